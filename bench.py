@@ -10,6 +10,12 @@ bytes of stripe data / time).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--stripes S]
                        [--op encode|decode|crc|encode_crc|mixed]
+                       [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints one JSON result
+line.  --dump-outputs DIR also writes what the last timed step computed as
+DIR/<name>.npy (see dump_outputs).  --full adds the legs that take runs of
+their own beyond the headline figure (today: the cpu_baseline leg, which
+a plain run reports as null).
 N>1 is launched by the driver via torch.distributed.run (one rank per GPU,
 RCCL); stripes shard across ranks as independent batches (weak scaling —
 the reference processes stripes independently too).
@@ -251,6 +257,37 @@ def read_traffic_calibration(workload):
     return None
 
 
+DUMP_CHUNK = 256          # bytes per sampled run
+DUMP_MAX_ELEMS = 1 << 20  # elements kept per output array
+DUMP_SEED = 20240607
+
+
+def dump_outputs(dirname, outputs):
+    """Write the arrays a caller of the timed path receives, as they stand
+    after the last timed step, to dirname/<name>.npy.  uint8 parts are stored
+    as float32 and 32-bit CRCs as float64 (both exact).  An output larger
+    than DUMP_MAX_ELEMS is reduced to a fixed sample: DUMP_CHUNK-element runs
+    at offsets drawn from a generator seeded with DUMP_SEED, so two runs with
+    the same arguments store the same positions (at most 8 MB per array)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in outputs.items():
+        flat = t.reshape(-1)
+        n = flat.numel()
+        if n > DUMP_MAX_ELEMS:
+            rng = np.random.default_rng(DUMP_SEED)
+            starts = np.sort(rng.choice(n // DUMP_CHUNK,
+                                        DUMP_MAX_ELEMS // DUMP_CHUNK,
+                                        replace=False)) * DUMP_CHUNK
+            flat = torch.cat([flat[o:o + DUMP_CHUNK]
+                              for o in starts.tolist()])
+        a = flat.cpu().numpy()
+        if a.dtype == np.int32:      # CRCs are kept in int32 tensors
+            a = a.view(np.uint32).astype(np.float64)
+        else:
+            a = a.astype(np.float32)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -262,12 +299,21 @@ def main():
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
                     help="gloo allows exercising the multi-rank path on a "
                          "single GPU (coordination on CPU; compute on GPU)")
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure "
+                         "(the cpu_baseline leg)")
+    ap.add_argument("--skip-cpu-baseline", action="store_true",
+                    help="with --full: leave the cpu_baseline leg out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the "
+                         "last step as DIR/<name>.npy")
     ap.add_argument("--validate", action="store_true",
                     help="after timing, bit-check recovered parts against "
                          "the original data (decode/mixed round-trip) and "
                          "the all-gather's own-rank slot")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     K, M, ERASED, S_default = OPS[args.op]
     S = args.stripes or S_default
@@ -311,6 +357,7 @@ def main():
     if args.op == "encode":
         def step():
             rs.encode_batch(data, parity)
+        outputs = {"parity": parity}
         alg_bytes_per_launch = S * STRIPE_BYTES * (K + M) // K
         metric = "GiB/s EC encode, ec(8,2) 64MiB stripes"
     elif args.op == "decode":
@@ -324,6 +371,7 @@ def main():
 
         def step():
             rs.recover_batch(frags, erased=ERASED, out=outs)
+        outputs = {f"recovered_part{i}": outs[i] for i in ERASED}
         alg_bytes_per_launch = S * PART_LEN * (K + len(ERASED))
         metric = "GiB/s EC decode(2 erasures), ec(8,2) 64MiB stripes"
     elif args.op == "crc":
@@ -333,6 +381,7 @@ def main():
 
         def step():
             lcrc.crc32_blocks(flat, 65536, out=crcs)
+        outputs = {"crc32": crcs}
         alg_bytes_per_launch = (S * STRIPE_BYTES +
                                 4 * (S * STRIPE_BYTES // 65536))
         metric = "GiB/s CRC32 per-64KiB-block"
@@ -365,6 +414,8 @@ def main():
             rs.encode_batch(data, parity)
             lcrc.crc32_blocks(pflat, 65536, out=pcrcs)
             main.wait_stream(crc_stream)
+        outputs = {"parity": parity, "data_crc32": dcrcs,
+                   "parity_crc32": pcrcs}
         alg_bytes_per_launch = S * STRIPE_BYTES * (K + M) // K  # encode leg
         metric = "GiB/s EC encode+CRC32 pipeline, ec(16,4) 64MiB stripes"
     else:  # mixed — config 5
@@ -397,6 +448,8 @@ def main():
                 for gi, i in enumerate(sorted(outs)):
                     src = outs[i] if gdev == "cuda" else outs[i].cpu()
                     torch.distributed.all_gather(gathered[gi], src)
+        outputs = {"parity": parity}
+        outputs.update({f"recovered_part{i}": outs[i] for i in ERASED})
         alg_bytes_per_launch = S * STRIPE_BYTES * (K + M) // K
         metric = ("GiB/s EC mixed encode+3-erasure decode, ec(32,6) "
                   "64MiB stripes")
@@ -427,6 +480,11 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
+        log(f"[rank 0] wrote {', '.join(sorted(outputs))} to "
+            f"{args.dump_outputs}")
 
     validated = None
     if args.validate and args.op in ("decode", "mixed"):
@@ -487,7 +545,7 @@ def main():
         }
 
     cpu_baseline = None
-    if n_gpus == 1 and not args.skip_cpu_baseline:
+    if args.full and n_gpus == 1 and not args.skip_cpu_baseline:
         log("[rank 0] timing CPU baseline (oracle, OpenMP)...")
         cpu_baseline = cpu_baseline_leg(args.op, K, M, ERASED)
 
