@@ -19,8 +19,9 @@
  * Ownership/threading: caller owns every buffer; no function retains state
  * except the engine object.  The per-call functions are pure and
  * thread-safe (matching bgjobs-worker concurrency in the reference,
- * network_main_thread.cc:230-234).  An engine is NOT thread-safe: use one
- * engine per stream/thread.
+ * network_main_thread.cc:230-234).  One engine is safe to use from several
+ * threads at once as long as concurrent calls pass distinct streams (each
+ * stream has its own call scratch); calls on one stream must not overlap.
  *
  * Error convention: 0 = success; negative = error (see LIZEC_E*).  The GF
  * layer itself only signals singular matrices, like the reference
@@ -160,8 +161,11 @@ void lizec_engine_destroy(lizec_engine *e);
 int lizec_engine_sync(lizec_engine *e);
 
 /* Batched EC encode/decode over device-resident stripes.  All stripes in a
- * batch share (srcs, dests, gftbls) — the reference likewise reuses one
- * cached table per (erasure pattern, k, m) (reed_solomon.h:194-198).
+ * batch share (srcs, dests, part_len).  This entry point also shares one
+ * gftbls across the batch — the reference likewise reuses one cached table
+ * per (erasure pattern, k, m) (reed_solomon.h:194-198); batches whose
+ * stripes carry different erasure patterns go through
+ * lizec_ec_encode_batch_multi below.
  *  part_len : bytes per part
  *  gftbls   : HOST pointer, 32*srcs*dests bytes (from lizec_rs_tables)
  *  src_dptrs: HOST array of num_stripes*srcs device addresses
@@ -187,6 +191,36 @@ int lizec_ec_plan_create(lizec_engine *e, uint64_t part_len, int srcs,
                          int num_stripes, lizec_plan **out);
 int lizec_ec_plan_run(lizec_plan *p, void *stream);
 void lizec_ec_plan_destroy(lizec_plan *p);
+
+/* Batched EC decode with a coefficient table PER STRIPE: one call (one
+ * launch per pass of 8 destinations) covers a batch of mixed erasure
+ * patterns — a rebuild after a disk loss (chunk_replicator.cc:139-196,
+ * where the lost disk held a different part of every chunk) or a batch of
+ * degraded reads (ec_read_plan.h:113-146, one pattern per read operation).
+ *  gftbls   : HOST pointer, ntables tables of 32*srcs*dests bytes each
+ *             (ISA-L layout, from lizec_rs_tables; a stripe that needs
+ *             fewer than `dests` outputs pads its table with zero rows)
+ *  ntables  : >= 1, and ntables*32*srcs*dests <= 2^30 bytes
+ *  tbl_index: HOST array, num_stripes entries, each < ntables; checked on
+ *             the host before anything is enqueued (LIZEC_EINVAL)
+ *  dst_dptrs: as above, but address 0 = do not write that output
+ * Everything else (srcs, dests, part_len uniform over the batch; stream
+ * and thread contract) is as for lizec_ec_encode_batch. */
+int lizec_ec_encode_batch_multi(lizec_engine *e, uint64_t part_len, int srcs,
+                                int dests, const uint8_t *gftbls, int ntables,
+                                const uint32_t *tbl_index,
+                                const uint64_t *src_dptrs,
+                                const uint64_t *dst_dptrs, int num_stripes,
+                                void *stream);
+
+/* Plan form of the above; run/destroy it with lizec_ec_plan_run and
+ * lizec_ec_plan_destroy. */
+int lizec_ec_plan_create_multi(lizec_engine *e, uint64_t part_len, int srcs,
+                               int dests, const uint8_t *gftbls, int ntables,
+                               const uint32_t *tbl_index,
+                               const uint64_t *src_dptrs,
+                               const uint64_t *dst_dptrs, int num_stripes,
+                               lizec_plan **out);
 
 /* Per-block CRC32 over a contiguous device buffer:
  *  dev_crcs_out[b] = lizec_crc32(seed, dev_buf + b*block_len, block_len)

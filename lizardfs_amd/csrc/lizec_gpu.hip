@@ -39,6 +39,7 @@
 	} while (0)
 
 #include "ec_kernel.h"
+#include "ec_kernel_multi.h"
 #include "crc_fold.h"
 
 /* Product kernel configuration (chosen by the variant A/B harness,
@@ -369,6 +370,16 @@ struct lizec_stream_ctx {
 	size_t h_cap = 0;               /* staging bytes */
 	hipEvent_t uploaded = nullptr;  /* staging consumed up to here */
 	bool ev_recorded = false;
+	/* multi-table batches only (lizec_ec_encode_batch_multi): per-stripe
+	 * table index and the packed tables, with a pinned staging buffer of
+	 * their own; guarded by the same `uploaded` event.  Never allocated
+	 * for callers of the single-table entry points. */
+	uint8_t *d_mtbls = nullptr;     /* ntables packed tables, grows */
+	size_t mtbls_cap = 0;           /* bytes */
+	uint32_t *d_mindex = nullptr;   /* tbl_index, grows */
+	size_t mindex_cap = 0;          /* in elements */
+	uint8_t *h_mstaging = nullptr;  /* pinned: packed tables + index */
+	size_t h_mcap = 0;              /* bytes */
 };
 
 struct lizec_engine {
@@ -387,6 +398,9 @@ static void ctx_free(lizec_stream_ctx &c) {
 	(void)hipFree(c.d_gftbls);
 	(void)hipFree(c.d_ptrs);
 	(void)hipHostFree(c.h_staging);
+	(void)hipFree(c.d_mtbls);
+	(void)hipFree(c.d_mindex);
+	(void)hipHostFree(c.h_mstaging);
 	if (c.uploaded) (void)hipEventDestroy(c.uploaded);
 	c = lizec_stream_ctx();
 }
@@ -440,6 +454,47 @@ static int ctx_acquire(lizec_engine *e, hipStream_t s, size_t ptrs,
 	return LIZEC_OK;
 }
 
+/* ctx_acquire plus the multi-table scratch: `tbl_bytes` of packed tables
+ * and `stripes` index entries on the device, and pinned staging for both.
+ * ctx_acquire has already waited out the previous call's uploads, so the
+ * buffers are free to grow (hipFree itself waits for running kernels). */
+static int ctx_acquire_multi(lizec_engine *e, hipStream_t s, size_t ptrs,
+                             size_t staging, size_t tbl_bytes, size_t stripes,
+                             lizec_stream_ctx **out) {
+	int r = ctx_acquire(e, s, ptrs, staging, out);
+	if (r != LIZEC_OK) return r;
+	lizec_stream_ctx &c = **out;
+	if (c.mtbls_cap < tbl_bytes) {
+		size_t cap = c.mtbls_cap ? c.mtbls_cap : (1 << 16);
+		while (cap < tbl_bytes) cap *= 2;
+		(void)hipFree(c.d_mtbls);
+		c.d_mtbls = nullptr;
+		c.mtbls_cap = 0;
+		LIZEC_CHECK(hipMalloc(&c.d_mtbls, cap));
+		c.mtbls_cap = cap;
+	}
+	if (c.mindex_cap < stripes) {
+		size_t cap = c.mindex_cap ? c.mindex_cap : (1 << 14);
+		while (cap < stripes) cap *= 2;
+		(void)hipFree(c.d_mindex);
+		c.d_mindex = nullptr;
+		c.mindex_cap = 0;
+		LIZEC_CHECK(hipMalloc(&c.d_mindex, cap * sizeof(uint32_t)));
+		c.mindex_cap = cap;
+	}
+	size_t want = tbl_bytes + stripes * sizeof(uint32_t);
+	if (c.h_mcap < want) {
+		size_t cap = c.h_mcap ? c.h_mcap : (1 << 17);
+		while (cap < want) cap *= 2;
+		(void)hipHostFree(c.h_mstaging);
+		c.h_mstaging = nullptr;
+		c.h_mcap = 0;
+		LIZEC_CHECK(hipHostMalloc(&c.h_mstaging, cap));
+		c.h_mcap = cap;
+	}
+	return LIZEC_OK;
+}
+
 /* A plan = a prepared batch: device-resident tables + pointer arrays.
  * Mirrors the reference's cached-matrix + read-plan structure
  * (reed_solomon.h:194-198, read_plan.h): build once per (erasure pattern,
@@ -451,6 +506,7 @@ struct lizec_plan {
 	uint8_t *d_tbls;
 	uint64_t *d_src;
 	uint64_t *d_dst;
+	uint32_t *d_index;   /* multi-table plans only: per-stripe table index */
 };
 
 extern "C" int lizec_gpu_count(void) {
@@ -644,6 +700,171 @@ extern "C" int lizec_ec_encode_batch(lizec_engine *e, uint64_t part_len,
 	                 (uint32_t)num_stripes, s);
 }
 
+/* Multi-table launch: same grid/tile/LDS shape as launch_ec. */
+template <int D>
+static void launch_ec_multi(uint32_t part_len, int srcs, int dest_base,
+                            const uint8_t *d_tbls, const uint32_t *d_index,
+                            const uint64_t *d_src, const uint64_t *d_dst,
+                            int dests_total, uint32_t nstripes,
+                            hipStream_t s) {
+	constexpr int CH = ec_chunks_for(D);
+	uint32_t tile_bytes = kChunkBytes * CH;
+	uint32_t tiles_per_part = (part_len + tile_bytes - 1) / tile_bytes;
+	uint32_t total_tiles = tiles_per_part * nstripes;
+	uint32_t grid = total_tiles < 1048576u ? total_tiles : 1048576u;
+	size_t lds = (size_t)D * srcs * kECTblBytes;
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(ec_encode_multi_kernel<D, CH, kECSwz, kECNtStore, kECNtLoad>),
+	                   dim3(grid), dim3(kThreads), lds, s,
+	                   part_len, srcs, dest_base, d_tbls, d_index, d_src,
+	                   d_dst, dests_total, tiles_per_part, total_tiles);
+}
+
+/* run_batch for per-stripe tables: the same split into passes of at most 8
+ * destinations; dest_base then offsets into every stripe's own table. */
+static int run_batch_multi(uint64_t part_len, int srcs, int dests,
+                           const uint8_t *d_tbls, const uint32_t *d_index,
+                           const uint64_t *d_src, const uint64_t *d_dst,
+                           uint32_t num_stripes, hipStream_t s) {
+	for (int base = 0; base < dests;) {
+		int d = dests - base;
+		if (d > 8) d = 8;
+#define LIZEC_LAUNCH_MULTI(D)                                              \
+	launch_ec_multi<D>((uint32_t)part_len, srcs, base, d_tbls, d_index,    \
+	                   d_src, d_dst, dests, num_stripes, s)
+		switch (d) {
+		case 1: LIZEC_LAUNCH_MULTI(1); break;
+		case 2: LIZEC_LAUNCH_MULTI(2); break;
+		case 3: LIZEC_LAUNCH_MULTI(3); break;
+		case 4: LIZEC_LAUNCH_MULTI(4); break;
+		case 5: LIZEC_LAUNCH_MULTI(5); break;
+		case 6: LIZEC_LAUNCH_MULTI(6); break;
+		case 7: LIZEC_LAUNCH_MULTI(7); break;
+		default: LIZEC_LAUNCH_MULTI(8); break;
+		}
+#undef LIZEC_LAUNCH_MULTI
+		base += d;
+	}
+	LIZEC_CHECK(hipGetLastError());
+	return LIZEC_OK;
+}
+
+/* check_batch_args plus the multi-table rules; runs entirely on the host,
+ * before anything is allocated or enqueued. */
+static int check_multi_args(uint64_t part_len, int srcs, int dests,
+                            const uint8_t *gftbls, int ntables,
+                            const uint32_t *tbl_index,
+                            const uint64_t *src_dptrs,
+                            const uint64_t *dst_dptrs, int num_stripes) {
+	int r = check_batch_args(part_len, srcs, dests, num_stripes);
+	if (r != LIZEC_OK) return r;
+	if (!gftbls || !tbl_index || !src_dptrs || !dst_dptrs) return LIZEC_EINVAL;
+	if (ntables < 1 ||
+	    (uint64_t)ntables * 32 * srcs * dests > (uint64_t)1 << 30)
+		return LIZEC_EINVAL;
+	for (int i = 0; i < num_stripes; ++i)
+		if (tbl_index[i] >= (uint32_t)ntables) return LIZEC_EINVAL;
+	return LIZEC_OK;
+}
+
+extern "C" int lizec_ec_encode_batch_multi(lizec_engine *e, uint64_t part_len,
+                                           int srcs, int dests,
+                                           const uint8_t *gftbls, int ntables,
+                                           const uint32_t *tbl_index,
+                                           const uint64_t *src_dptrs,
+                                           const uint64_t *dst_dptrs,
+                                           int num_stripes, void *stream) {
+	if (!e) return LIZEC_EINVAL;
+	int r = check_multi_args(part_len, srcs, dests, gftbls, ntables,
+	                         tbl_index, src_dptrs, dst_dptrs, num_stripes);
+	if (r != LIZEC_OK) return r;
+	hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+	LIZEC_CHECK(hipSetDevice(e->device));
+
+	size_t nsrc = (size_t)num_stripes * srcs;
+	size_t ndst = (size_t)num_stripes * dests;
+	size_t ntbl = (size_t)ntables * srcs * dests;   /* 32-byte tables */
+	size_t tbl_bytes = ntbl * kECTblBytes;
+	lizec_stream_ctx *c;
+	r = ctx_acquire_multi(e, s, nsrc + ndst, (nsrc + ndst) * 8, tbl_bytes,
+	                      (size_t)num_stripes, &c);
+	if (r != LIZEC_OK) return r;
+	uint64_t *d_src = c->d_ptrs;
+	uint64_t *d_dst = c->d_ptrs + nsrc;
+	/* pointer arrays go through the shared staging buffer (past its
+	 * single-table area), tables + index through the multi one */
+	uint64_t *pstage = (uint64_t *)(c->h_staging + (size_t)kECTblBytes * 32 * 32);
+	uint8_t *tstage = c->h_mstaging;
+	uint32_t *istage = (uint32_t *)(c->h_mstaging + tbl_bytes);
+	for (size_t i = 0; i < ntbl; ++i)
+		pack_mixed_radix(gftbls + i * 32, tstage + i * kECTblBytes);
+	memcpy(istage, tbl_index, (size_t)num_stripes * 4);
+	memcpy(pstage, src_dptrs, nsrc * 8);
+	memcpy(pstage + nsrc, dst_dptrs, ndst * 8);
+	LIZEC_CHECK(hipMemcpyAsync(c->d_mtbls, tstage, tbl_bytes,
+	                           hipMemcpyHostToDevice, s));
+	LIZEC_CHECK(hipMemcpyAsync(c->d_mindex, istage, (size_t)num_stripes * 4,
+	                           hipMemcpyHostToDevice, s));
+	LIZEC_CHECK(hipMemcpyAsync(d_src, pstage, (nsrc + ndst) * 8,
+	                           hipMemcpyHostToDevice, s));
+	LIZEC_CHECK(hipEventRecord(c->uploaded, s));
+	c->ev_recorded = true;
+
+	return run_batch_multi(part_len, srcs, dests, c->d_mtbls, c->d_mindex,
+	                       d_src, d_dst, (uint32_t)num_stripes, s);
+}
+
+extern "C" int lizec_ec_plan_create_multi(lizec_engine *e, uint64_t part_len,
+                                          int srcs, int dests,
+                                          const uint8_t *gftbls, int ntables,
+                                          const uint32_t *tbl_index,
+                                          const uint64_t *src_dptrs,
+                                          const uint64_t *dst_dptrs,
+                                          int num_stripes, lizec_plan **out) {
+	*out = nullptr;
+	if (!e) return LIZEC_EINVAL;
+	int r = check_multi_args(part_len, srcs, dests, gftbls, ntables,
+	                         tbl_index, src_dptrs, dst_dptrs, num_stripes);
+	if (r != LIZEC_OK) return r;
+	LIZEC_CHECK(hipSetDevice(e->device));
+	size_t nsrc = (size_t)num_stripes * srcs;
+	size_t ndst = (size_t)num_stripes * dests;
+	size_t ntbl = (size_t)ntables * srcs * dests;
+	size_t tbl_bytes = ntbl * kECTblBytes;
+	uint8_t *packed = (uint8_t *)malloc(tbl_bytes);
+	if (!packed) return LIZEC_ENOMEM;
+	for (size_t i = 0; i < ntbl; ++i)
+		pack_mixed_radix(gftbls + i * 32, packed + i * kECTblBytes);
+	lizec_plan *p = new lizec_plan();
+	p->e = e;
+	p->part_len = part_len;
+	p->srcs = srcs;
+	p->dests = dests;
+	p->num_stripes = num_stripes;
+	if (hipMalloc(&p->d_tbls, tbl_bytes) != hipSuccess ||
+	    hipMalloc(&p->d_src, nsrc * 8) != hipSuccess ||
+	    hipMalloc(&p->d_dst, ndst * 8) != hipSuccess ||
+	    hipMalloc(&p->d_index, (size_t)num_stripes * 4) != hipSuccess) {
+		free(packed);
+		lizec_ec_plan_destroy(p);
+		return LIZEC_ENOMEM;
+	}
+	bool ok = hipMemcpy(p->d_tbls, packed, tbl_bytes,
+	                    hipMemcpyHostToDevice) == hipSuccess &&
+	          hipMemcpy(p->d_index, tbl_index, (size_t)num_stripes * 4,
+	                    hipMemcpyHostToDevice) == hipSuccess &&
+	          hipMemcpy(p->d_src, src_dptrs, nsrc * 8,
+	                    hipMemcpyHostToDevice) == hipSuccess &&
+	          hipMemcpy(p->d_dst, dst_dptrs, ndst * 8,
+	                    hipMemcpyHostToDevice) == hipSuccess;
+	free(packed);
+	if (!ok) {
+		lizec_ec_plan_destroy(p);
+		return LIZEC_EHIP;
+	}
+	*out = p;
+	return LIZEC_OK;
+}
+
 extern "C" int lizec_ec_plan_create(lizec_engine *e, uint64_t part_len,
                                     int srcs, int dests,
                                     const uint8_t *gftbls,
@@ -689,6 +910,10 @@ extern "C" int lizec_ec_plan_run(lizec_plan *p, void *stream) {
 	if (!p) return LIZEC_EINVAL;
 	hipStream_t s = stream ? (hipStream_t)stream : p->e->stream;
 	LIZEC_CHECK(hipSetDevice(p->e->device));
+	if (p->d_index)
+		return run_batch_multi(p->part_len, p->srcs, p->dests, p->d_tbls,
+		                       p->d_index, p->d_src, p->d_dst,
+		                       (uint32_t)p->num_stripes, s);
 	return run_batch(p->part_len, p->srcs, p->dests, p->d_tbls, p->d_src,
 	                 p->d_dst, (uint32_t)p->num_stripes, s);
 }
@@ -698,6 +923,7 @@ extern "C" void lizec_ec_plan_destroy(lizec_plan *p) {
 	(void)hipFree(p->d_tbls);
 	(void)hipFree(p->d_src);
 	(void)hipFree(p->d_dst);
+	(void)hipFree(p->d_index);
 	delete p;
 }
 

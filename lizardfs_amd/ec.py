@@ -10,6 +10,7 @@ slice_traits.h:183-197), None input = implicit zero part
 (reed_solomon.h:194-198).
 """
 import ctypes
+import hashlib
 
 import numpy as np
 import torch
@@ -20,6 +21,131 @@ from . import slice_traits
 
 def _tables_cache_key(k, m, present, nonnull, needed):
     return (k, m, present, nonnull, needed)
+
+
+_POPCOUNT8 = np.array([bin(i).count("1") for i in range(256)], np.int64)
+
+
+def _pattern_masks(sets, nparts, what):
+    """Per-stripe index sets -> (uint64 bitmask [S], set size [S]).  An
+    integer ndarray [S, n] (one row per stripe) takes a vectorised path."""
+    if isinstance(sets, np.ndarray) and sets.ndim == 2 and \
+            sets.dtype.kind in "iu":
+        if sets.size and (sets.min() < 0 or sets.max() >= nparts):
+            raise ValueError(f"{what}: part index out of [0,{nparts})")
+        bits = np.uint64(1) << sets.astype(np.uint64)
+        masks = np.bitwise_or.reduce(bits, axis=1) if sets.shape[1] else \
+            np.zeros(sets.shape[0], np.uint64)
+        masks = masks.astype(np.uint64)
+    else:
+        masks = np.empty(len(sets), np.uint64)
+        for s, idx in enumerate(sets):
+            v = 0
+            for i in idx:
+                i = int(i)
+                if not 0 <= i < nparts:
+                    raise ValueError(
+                        f"{what}[{s}]: part index {i} out of [0,{nparts})")
+                v |= 1 << i
+            masks[s] = v
+    masks = np.ascontiguousarray(masks)
+    sizes = _POPCOUNT8[masks.view(np.uint8).reshape(-1, 8)].sum(axis=1)
+    return masks, sizes
+
+
+# (k, m, erased mask, want mask) -> (ISA-L table bytes, rebuilt parts): the
+# matrix inversion behind a pattern is done once per process, like the
+# reference's per-pattern matrix cache (reed_solomon.h:194-198).
+_pattern_cache = {}
+_PATTERN_CACHE_MAX = 16384
+
+
+def _pattern_table(k, m, em, wm):
+    key = (k, m, em, wm)
+    t = _pattern_cache.get(key)
+    if t is None:
+        nparts = k + m
+        present = ((1 << nparts) - 1) & ~em
+        tbl = np.zeros(32 * 32 * 32, np.uint8)
+        ic = ctypes.c_int()
+        oc = ctypes.c_int()
+        L.check(L.lib().lizec_rs_tables(
+            k, m, present, present, wm,
+            tbl.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+            ctypes.byref(ic), ctypes.byref(oc)), "lizec_rs_tables")
+        assert ic.value == k
+        parts = [i for i in range(nparts) if (wm >> i) & 1]
+        assert oc.value == len(parts)
+        t = (tbl[:32 * k * oc.value].copy(), parts)
+        if len(_pattern_cache) >= _PATTERN_CACHE_MAX:
+            _pattern_cache.clear()
+        _pattern_cache[key] = t
+    return t
+
+
+def build_pattern_tables(k, m, erased, want=None):
+    """Recover tables for a batch whose stripes carry their own erasure
+    patterns (host-side only; needs no GPU).
+
+    erased: length-S sequence of index sets, exactly m indices each
+      (reed_solomon.h:95), or an integer ndarray [S, m].
+    want: length-S sequence of non-empty subsets of the matching erased
+      set (default: the erased sets).
+    Returns (tables, index, slots):
+      tables uint8 [P, 32*k*oc] — one ISA-L-layout table per distinct
+        (erased, want) pair, oc = the largest want size; a pattern wanting
+        fewer parts has zero rows for its unused outputs;
+      index  uint32 [S] — stripe -> row of `tables`;
+      slots  int64 [S, oc] — part rebuilt in each output slot, ascending,
+        -1 for an unused slot.
+    """
+    tables, index, pslots, _ = _pattern_tables(k, m, erased, want)
+    return tables, index, pslots[index]
+
+
+def _pattern_tables(k, m, erased, want):
+    """build_pattern_tables, per pattern: (tables [P, .], index [S],
+    slots [P, oc], erased masks [P])."""
+    nparts = k + m
+    emask, esize = _pattern_masks(erased, nparts, "erased")
+    S = emask.shape[0]
+    if S == 0:
+        raise ValueError("no stripes")
+    if np.any(esize != m):
+        s = int(np.argmax(esize != m))
+        raise ValueError(f"erased[{s}]: exactly m={m} erased parts required "
+                         f"(got {int(esize[s])})")
+    if want is None or want is erased:
+        wmask, wsize = emask, esize
+    else:
+        wmask, wsize = _pattern_masks(want, nparts, "want")
+        if wmask.shape[0] != S:
+            raise ValueError(f"want has {wmask.shape[0]} entries, erased {S}")
+        if np.any(wsize == 0):
+            raise ValueError(f"want[{int(np.argmax(wsize == 0))}] is empty")
+        bad = (wmask & ~emask) != 0
+        if np.any(bad):
+            raise ValueError(f"want[{int(np.argmax(bad))}] must be a subset "
+                             f"of erased")
+    oc = int(wsize.max())
+    if 2 * nparts <= 64:
+        # both masks fit one word: a 1-D unique is much faster at large S
+        sh = np.uint64(nparts)
+        keys, index = np.unique((emask << sh) | wmask, return_inverse=True)
+        pairs = np.stack([keys >> sh,
+                          keys & np.uint64((1 << nparts) - 1)], axis=1)
+    else:
+        pairs, index = np.unique(np.stack([emask, wmask], axis=1), axis=0,
+                                 return_inverse=True)
+    index = np.ascontiguousarray(index.reshape(-1).astype(np.uint32))
+    P = pairs.shape[0]
+    tables = np.zeros((P, 32 * k * oc), np.uint8)
+    pslots = np.full((P, oc), -1, np.int64)
+    for p in range(P):
+        tbl, parts = _pattern_table(k, m, int(pairs[p, 0]), int(pairs[p, 1]))
+        tables[p, :tbl.size] = tbl
+        pslots[p, :len(parts)] = parts
+    return tables, index, pslots, np.ascontiguousarray(pairs[:, 0])
 
 
 class ReedSolomon:
@@ -228,6 +354,101 @@ class ReedSolomon:
         self._run(plen, tbl, ic, oc, np.ascontiguousarray(src.ravel()),
                   np.ascontiguousarray(dst.ravel()), S, plan_key=plan_key)
         return outs
+
+    def recover_batch_mixed(self, fragments, erased, want=None, out=None):
+        """Recover missing parts for a batch whose stripes each carry their
+        own erasure pattern, in one call (lizec_ec_encode_batch_multi).
+
+        fragments: list of k+m uint8 CUDA tensors [S, L] (strided row views
+          allowed, as in recover_batch).  None is not allowed: every stripe
+          reads exactly k sources.  Rows of a part erased in a stripe are
+          ignored; a stripe's sources are its k surviving parts, ascending.
+        erased / want: per-stripe index sets, see build_pattern_tables.
+        out: optional uint8 CUDA tensor [S, oc, L] (contiguous); supplying
+          it makes the buffers stable, so the plan is cached.
+        Returns (out [S, oc, L], slots [S, oc]): out[s, j] holds part
+        slots[s, j]; slots of -1 are passed as address 0 and never written.
+        """
+        nparts = self.k + self.m
+        if len(fragments) != nparts:
+            raise ValueError(f"need {nparts} fragments")
+        S = plen = dev = None
+        bases = np.empty(nparts, np.uint64)
+        strides = np.empty(nparts, np.uint64)
+        for i, t in enumerate(fragments):
+            if t is None:
+                raise ValueError(f"fragment {i} is None: recover_batch_mixed "
+                                 f"needs all k+m tensors")
+            s, l, rstride = self._frag_geom(t, f"fragment {i}")
+            if S is not None and (s, l) != (S, plen):
+                raise ValueError(
+                    f"fragment {i} is [{s}, {l}], expected [{S}, {plen}]")
+            S, plen, dev = s, l, t.device
+            bases[i] = t.data_ptr()
+            strides[i] = rstride
+        if plen % 16:
+            raise ValueError("part length must be a multiple of 16")
+
+        tables, index, pslots, pemask = _pattern_tables(self.k, self.m,
+                                                        erased, want)
+        slots = pslots[index]
+        if index.shape[0] != S:
+            raise ValueError(f"{index.shape[0]} patterns for {S} stripes")
+        oc = slots.shape[1]
+        if out is not None:
+            self._check_part(out, "out")
+            if tuple(out.shape) != (S, oc, plen):
+                raise ValueError(f"out must be [S={S}, oc={oc}, L={plen}], "
+                                 f"got {tuple(out.shape)}")
+            outs = out
+        else:
+            outs = torch.empty((S, oc, plen), dtype=torch.uint8, device=dev)
+
+        def call(fn, last, what):
+            # sources: each pattern's k surviving parts in ascending order
+            palive = np.array(
+                [[i for i in range(nparts) if not (int(e) >> i) & 1]
+                 for e in pemask], np.intp)
+            alive = palive[index]                              # [S, k]
+            rows = np.arange(S, dtype=np.uint64)[:, None]
+            src = np.ascontiguousarray(bases[alive] + rows * strides[alive])
+            dst = (np.uint64(outs.data_ptr()) +
+                   np.arange(S * oc, dtype=np.uint64).reshape(S, oc) *
+                   np.uint64(plen))
+            dst = np.ascontiguousarray(np.where(slots >= 0, dst,
+                                                np.uint64(0)))
+            u8p = ctypes.POINTER(ctypes.c_uint8)
+            u32p = ctypes.POINTER(ctypes.c_uint32)
+            u64p = ctypes.POINTER(ctypes.c_uint64)
+            L.check(fn(self._engine, plen, self.k, oc,
+                       tables.ctypes.data_as(u8p), tables.shape[0],
+                       index.ctypes.data_as(u32p), src.ctypes.data_as(u64p),
+                       dst.ctypes.data_as(u64p), S, last), what)
+
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if out is None:
+            call(self._lib.lizec_ec_encode_batch_multi,
+                 ctypes.c_void_p(stream), "lizec_ec_encode_batch_multi")
+            return outs, slots
+        # stable buffers: the pointer arrays are only built on a plan miss
+        h = hashlib.blake2b(digest_size=16)
+        h.update(index.tobytes())
+        h.update(pslots.tobytes())
+        h.update(pemask.tobytes())
+        plan_key = ("mix", h.digest(), tuple(int(b) for b in bases),
+                    tuple(int(x) for x in strides), outs.data_ptr(), S, plen)
+        plan = self._plans.get(plan_key)
+        if plan is None:
+            while len(self._plans) >= 64:   # bound device-side state
+                oldest = next(iter(self._plans))
+                self._lib.lizec_ec_plan_destroy(self._plans.pop(oldest))
+            plan = ctypes.c_void_p()
+            call(self._lib.lizec_ec_plan_create_multi, ctypes.byref(plan),
+                 "lizec_ec_plan_create_multi")
+            self._plans[plan_key] = plan
+        L.check(self._lib.lizec_ec_plan_run(plan, ctypes.c_void_p(stream)),
+                "lizec_ec_plan_run")
+        return outs, slots
 
     def sync(self):
         L.check(self._lib.lizec_engine_sync(self._engine))

@@ -78,6 +78,18 @@ def lib():
         ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, u8p,
         ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
         ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
+    L.lizec_ec_encode_batch_multi.restype = ctypes.c_int
+    L.lizec_ec_encode_batch_multi.argtypes = [
+        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, u8p,
+        ctypes.c_int, ctypes.POINTER(ctypes.c_uint32),
+        ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+        ctypes.c_int, ctypes.c_void_p]
+    L.lizec_ec_plan_create_multi.restype = ctypes.c_int
+    L.lizec_ec_plan_create_multi.argtypes = [
+        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, u8p,
+        ctypes.c_int, ctypes.POINTER(ctypes.c_uint32),
+        ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+        ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
     L.lizec_ec_plan_run.restype = ctypes.c_int
     L.lizec_ec_plan_run.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     L.lizec_ec_plan_destroy.argtypes = [ctypes.c_void_p]
