@@ -171,6 +171,11 @@ int lizec_engine_sync(lizec_engine *e);
  *  src_dptrs: HOST array of num_stripes*srcs device addresses
  *             (stripe-major: stripe s, input j at [s*srcs + j])
  *  dst_dptrs: HOST array of num_stripes*dests device addresses
+ * Every part address must be 16-byte aligned (the kernels move parts in
+ * 16-byte vectors), and part_len a multiple of 16; otherwise the call
+ * returns LIZEC_EINVAL from the host and enqueues nothing.  The same rule
+ * holds for the plan and multi-table forms below, where a destination
+ * address of 0 stays legal.
  * Covers encode (a1/a6: chunk_writer.cc:365-402), degraded-read decode
  * (ec_read_plan.h:113-146) and replicator recovery
  * (chunk_replicator.cc:139-196) — all three reduce to ec_encode_data with
@@ -225,7 +230,15 @@ int lizec_ec_plan_create_multi(lizec_engine *e, uint64_t part_len, int srcs,
 /* Per-block CRC32 over a contiguous device buffer:
  *  dev_crcs_out[b] = lizec_crc32(seed, dev_buf + b*block_len, block_len)
  * The chunkserver's per-64KiB-block gate (hddspacemgr.cc:1918-1920, scrub
- * :2148-2212, replicate chunk_replicator.cc:189) in batch form. */
+ * :2148-2212, replicate chunk_replicator.cc:189) in batch form.
+ *  block_len: a multiple of 1024, below 2^27 (128 MiB): the combine step
+ *             appends zero runs of up to block_len/2 bytes, and its matrix
+ *             bank covers runs shorter than 2^26
+ *  dev_buf  : at least 4-byte aligned.  16-byte aligned buffers take the
+ *             vector-load kernels; 4- and 8-byte aligned ones (INTERLEAVED
+ *             chunk format) are read with dword loads at every block_len
+ * Anything else returns LIZEC_EINVAL from the host; nothing is enqueued
+ * and dev_crcs_out is not written. */
 int lizec_crc32_batch(lizec_engine *e, const void *dev_buf, uint32_t block_len,
                       uint64_t nblocks, uint32_t seed, uint32_t *dev_crcs_out,
                       void *stream);

@@ -23,16 +23,28 @@ def crc32_combine(crc1, crc2, len2):
     return L.lib().lizec_crc32_combine(crc1, crc2, len2)
 
 
+# lizec_crc32_batch's bound: its combine matrices cover zero runs of up to
+# block_len / 2 < 2^26 bytes
+MAX_BLOCK_LEN = 1 << 27
+
+
 def crc32_blocks(buf, block_len=slice_traits.BLOCK_SIZE, seed=0, out=None,
                  device=None):
     """CRC32 of consecutive fixed-size blocks of a device buffer.
 
     buf: uint8 CUDA tensor, flat or any shape with numel % block_len == 0.
     Returns int32 CUDA tensor [nblocks] holding the CRCs (bit pattern; view
-    as uint32).  block_len must be a multiple of 1024.
+    as uint32).  block_len must be a multiple of 1024 below 2^27, and buf
+    at least 4-byte aligned (lizec.h, lizec_crc32_batch).
     """
     if buf.dtype != torch.uint8 or not buf.is_cuda or not buf.is_contiguous():
         raise ValueError("buf must be a contiguous CUDA uint8 tensor")
+    if block_len <= 0 or block_len % 1024 or block_len >= MAX_BLOCK_LEN:
+        raise ValueError(f"block_len must be a multiple of 1024 below "
+                         f"{MAX_BLOCK_LEN} (got {block_len})")
+    if buf.data_ptr() % 4:
+        raise ValueError(f"buf must be 4-byte aligned "
+                         f"(address {buf.data_ptr():#x})")
     n = buf.numel()
     if n % block_len:
         raise ValueError("buffer size must be a multiple of block_len")

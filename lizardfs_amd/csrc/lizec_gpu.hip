@@ -81,14 +81,18 @@ static void pack_mixed_radix(const uint8_t *t, uint8_t *q) {
  *               the generic kernel uses T0..T3, the fast path T0..T7 by
  *               default or T0..T15 under LIZEC_CRC_SLICE=16)
  *  [then]       u32[26][32]: advance matrices M_i = "append 2^i zero
- *               BYTES", i = 0..25 (supports block_len < 64 MiB)          */
+ *               BYTES", i = 0..25: zero runs shorter than 2^26 bytes,
+ *               which bounds block_len below 2^27 (lizec_crc32_batch)    */
 constexpr int kCrcTabWords = 16 * 256;  /* slicing-by-16 tables T0..T15 */
 constexpr int kCrcMatCount = 26;
 constexpr int kCrcConstWords = kCrcTabWords + kCrcMatCount * 32;
 
 /* One wave per block: lane l owns segment [l*seg, l*seg+seg) of the block
  * (seg = block_len/64, multiple of 16 enforced by the host).  Lane 0 seeds;
- * the shfl tree folds 64 segment CRCs into the block CRC. */
+ * the shfl tree folds 64 segment CRCs into the block CRC.  AL16=false
+ * reads the buffer with dword loads, for bases that are only 4-byte
+ * aligned (crc_ld16 in crc_fold.h). */
+template <bool AL16 = true>
 __global__ __launch_bounds__(kThreads) void crc32_blocks_kernel(
     const uint8_t *__restrict__ buf, uint32_t block_len, uint64_t nblocks,
     uint32_t seed, const uint32_t *__restrict__ crc_const,
@@ -112,7 +116,7 @@ __global__ __launch_bounds__(kThreads) void crc32_blocks_kernel(
 		const uint8_t *p = buf + blk * block_len + (uint32_t)lane * seg;
 		uint32_t crc = (lane == 0 ? seed : 0u) ^ 0xFFFFFFFFu;
 		for (uint32_t i = 0; i < seg; i += 16) {
-			uint4 w = *(const uint4 *)(p + i);
+			uint4 w = crc_ld16<AL16>(p + i);
 #define LIZEC_CRC_WORD(x)                                              \
 	do {                                                               \
 		uint32_t u = crc ^ (x);                                        \
@@ -601,6 +605,18 @@ static int check_batch_args(uint64_t part_len, int srcs, int dests,
 	return LIZEC_OK;
 }
 
+/* The kernels read and write every part with 16-byte vector accesses at
+ * 16-byte offsets, so every part address must be 16-byte aligned (0, the
+ * multi-table "skip this output", passes).  Host only, before anything is
+ * allocated or enqueued. */
+static int check_part_addrs(const uint64_t *src_dptrs, size_t nsrc,
+                            const uint64_t *dst_dptrs, size_t ndst) {
+	uint64_t bits = 0;
+	for (size_t i = 0; i < nsrc; ++i) bits |= src_dptrs[i];
+	for (size_t i = 0; i < ndst; ++i) bits |= dst_dptrs[i];
+	return (bits & 15) ? LIZEC_EINVAL : LIZEC_OK;
+}
+
 template <int D>
 static void launch_ec(uint32_t part_len, int srcs, int dest_base,
                       const uint8_t *d_tbls, const uint64_t *d_src,
@@ -671,11 +687,13 @@ extern "C" int lizec_ec_encode_batch(lizec_engine *e, uint64_t part_len,
 	if (!e) return LIZEC_EINVAL;
 	int r = check_batch_args(part_len, srcs, dests, num_stripes);
 	if (r != LIZEC_OK) return r;
+	size_t nsrc = (size_t)num_stripes * srcs;
+	size_t ndst = (size_t)num_stripes * dests;
+	r = check_part_addrs(src_dptrs, nsrc, dst_dptrs, ndst);
+	if (r != LIZEC_OK) return r;
 	hipStream_t s = stream ? (hipStream_t)stream : e->stream;
 	LIZEC_CHECK(hipSetDevice(e->device));
 
-	size_t nsrc = (size_t)num_stripes * srcs;
-	size_t ndst = (size_t)num_stripes * dests;
 	lizec_stream_ctx *c;
 	r = ctx_acquire(e, s, nsrc + ndst, (nsrc + ndst) * 8, &c);
 	if (r != LIZEC_OK) return r;
@@ -763,7 +781,8 @@ static int check_multi_args(uint64_t part_len, int srcs, int dests,
 		return LIZEC_EINVAL;
 	for (int i = 0; i < num_stripes; ++i)
 		if (tbl_index[i] >= (uint32_t)ntables) return LIZEC_EINVAL;
-	return LIZEC_OK;
+	return check_part_addrs(src_dptrs, (size_t)num_stripes * srcs, dst_dptrs,
+	                        (size_t)num_stripes * dests);
 }
 
 extern "C" int lizec_ec_encode_batch_multi(lizec_engine *e, uint64_t part_len,
@@ -875,6 +894,10 @@ extern "C" int lizec_ec_plan_create(lizec_engine *e, uint64_t part_len,
 	if (!e) return LIZEC_EINVAL;
 	int r = check_batch_args(part_len, srcs, dests, num_stripes);
 	if (r != LIZEC_OK) return r;
+	size_t nsrc = (size_t)num_stripes * srcs;
+	size_t ndst = (size_t)num_stripes * dests;
+	r = check_part_addrs(src_dptrs, nsrc, dst_dptrs, ndst);
+	if (r != LIZEC_OK) return r;
 	LIZEC_CHECK(hipSetDevice(e->device));
 	lizec_plan *p = new lizec_plan();
 	p->e = e;
@@ -882,8 +905,6 @@ extern "C" int lizec_ec_plan_create(lizec_engine *e, uint64_t part_len,
 	p->srcs = srcs;
 	p->dests = dests;
 	p->num_stripes = num_stripes;
-	size_t nsrc = (size_t)num_stripes * srcs;
-	size_t ndst = (size_t)num_stripes * dests;
 	if (hipMalloc(&p->d_tbls, (size_t)kECTblBytes * srcs * dests) != hipSuccess ||
 	    hipMalloc(&p->d_src, nsrc * 8) != hipSuccess ||
 	    hipMalloc(&p->d_dst, ndst * 8) != hipSuccess) {
@@ -934,6 +955,17 @@ extern "C" int lizec_crc32_batch(lizec_engine *e, const void *dev_buf,
 	if (!e || !dev_buf || !dev_crcs_out || nblocks < 1) return LIZEC_EINVAL;
 	/* one wave per block, 64 equal lane segments, 16B vector loads */
 	if (block_len == 0 || (block_len & 1023)) return LIZEC_EINVAL;
+	/* The matrix bank holds M_0..M_{kCrcMatCount-1}, so crc_advance can
+	 * append any zero run shorter than 2^kCrcMatCount bytes.  The longest
+	 * run a kernel asks for is block_len / 2: the last step of the shfl
+	 * tree advances by 32 lane segments (32 * span / 64 = span / 2, with
+	 * span = block_len / C), and the span splice of a C-chain kernel by
+	 * span = block_len / C <= block_len / 2.  Hence block_len / 2 <
+	 * 2^kCrcMatCount, i.e. block_len < 2^27; a longer block would index
+	 * past the bank and return a wrong CRC. */
+	if (block_len >= (2u << kCrcMatCount)) return LIZEC_EINVAL;
+	/* every kernel reads the buffer in 32-bit words or wider */
+	if ((uintptr_t)dev_buf & 3) return LIZEC_EINVAL;
 	hipStream_t s = stream ? (hipStream_t)stream : e->stream;
 	LIZEC_CHECK(hipSetDevice(e->device));
 	uint64_t groups = (nblocks + 3) / 4;
@@ -957,6 +989,23 @@ extern "C" int lizec_crc32_batch(lizec_engine *e, const void *dev_buf,
 	 * robust across boxes.  Default off; env opt-in for A/B. */
 	bool pfld = pf && atoi(pf) != 0;
 	bool al16 = (((uintptr_t)dev_buf | block_len) & 15) == 0;
+	/* A base that is 4- but not 16-byte aligned (the INTERLEAVED chunk
+	 * format) may only reach kernels that load dwords: the fold kernels'
+	 * AL16=false forms where the block splits into whole bursts, the
+	 * generic kernel's otherwise.  The slicing kernels below load 16-byte
+	 * vectors whatever the base. */
+	if (!al16 && (!fold || block_len % (64 * 16 * 8) != 0)) {
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(crc32_blocks_kernel<false>),
+		                   dim3(grid), dim3(kThreads), 0, s,
+		                   (const uint8_t *)dev_buf, block_len, nblocks,
+		                   seed, e->d_crc_const, dev_crcs_out);
+		LIZEC_CHECK(hipGetLastError());
+		return LIZEC_OK;
+	}
+	/* ...and the fold kernels have dword forms for one chain, and for two
+	 * where the block splits into two spans of whole bursts */
+	if (!al16 && !(chains == 2 && block_len % (2 * 64 * 16 * 8) == 0))
+		chains = 1;
 	/* carry-less-folding path (default): block must split into C spans of
 	 * whole 64-lane x BV*16-byte bursts (BV=8) */
 	if (fold && block_len % ((uint32_t)chains * 64 * 16 * 8) == 0 &&
@@ -1078,8 +1127,9 @@ extern "C" int lizec_crc32_batch(lizec_engine *e, const void *dev_buf,
 		                   (const uint8_t *)dev_buf, block_len, nblocks,
 		                   seed, e->d_crc_const, dev_crcs_out);
 	else
-		hipLaunchKernelGGL(crc32_blocks_kernel, dim3(grid), dim3(kThreads),
-		                   0, s, (const uint8_t *)dev_buf, block_len, nblocks,
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(crc32_blocks_kernel<true>),
+		                   dim3(grid), dim3(kThreads), 0, s,
+		                   (const uint8_t *)dev_buf, block_len, nblocks,
 		                   seed, e->d_crc_const, dev_crcs_out);
 	LIZEC_CHECK(hipGetLastError());
 	return LIZEC_OK;

@@ -229,6 +229,15 @@ class ReedSolomon:
             raise ValueError(f"{what} must be a contiguous CUDA uint8 tensor")
 
     @staticmethod
+    def _check_aligned(t, what, row_stride=0):
+        """The kernels move parts in 16-byte vectors (lizec.h): every part
+        row of `t` must start on a 16-byte boundary."""
+        if t.data_ptr() % 16 or row_stride % 16:
+            raise ValueError(f"{what}: part rows must be 16-byte aligned "
+                             f"(address {t.data_ptr():#x}, row stride "
+                             f"{row_stride})")
+
+    @staticmethod
     def _frag_geom(t, what):
         """[S, L] fragment, possibly a strided view (e.g. data[:, i, :]):
         rows must be contiguous; returns (S, L, row_stride_bytes)."""
@@ -252,6 +261,7 @@ class ReedSolomon:
             raise ValueError(f"data has {k} parts, expected {self.k}")
         if plen % 16:
             raise ValueError("part length must be a multiple of 16")
+        self._check_aligned(data, "data")
         caller_parity = parity is not None
         if parity is None:
             parity = torch.empty((S, self.m, plen), dtype=torch.uint8,
@@ -261,6 +271,7 @@ class ReedSolomon:
             if tuple(parity.shape) != (S, self.m, plen):
                 raise ValueError(f"parity must be [S={S}, m={self.m}, "
                                  f"L={plen}], got {tuple(parity.shape)}")
+            self._check_aligned(parity, "parity")
 
         dmask = (1 << self.k) - 1
         pmask = ((1 << self.m) - 1) << self.k
@@ -309,10 +320,12 @@ class ReedSolomon:
                 continue
             present |= 1 << i
             if fragments[i] is not None:
-                s, l, _ = self._frag_geom(fragments[i], f"fragment {i}")
+                s, l, rs = self._frag_geom(fragments[i], f"fragment {i}")
                 if S is not None and (s, l) != (S, plen):
                     raise ValueError(
                         f"fragment {i} is [{s}, {l}], expected [{S}, {plen}]")
+                self._check_aligned(fragments[i], f"fragment {i}",
+                                    rs if s > 1 else 0)
                 nonnull |= 1 << i
                 S, plen = s, l
                 dev = fragments[i].device
@@ -334,6 +347,7 @@ class ReedSolomon:
                 if tuple(outs[i].shape) != (S, plen):
                     raise ValueError(f"out[{i}] must be [S={S}, L={plen}], "
                                      f"got {tuple(outs[i].shape)}")
+                self._check_aligned(outs[i], f"out[{i}]")
         else:
             outs = {i: torch.empty((S, plen), dtype=torch.uint8, device=dev)
                     for i in sorted(want)}
@@ -383,6 +397,7 @@ class ReedSolomon:
             if S is not None and (s, l) != (S, plen):
                 raise ValueError(
                     f"fragment {i} is [{s}, {l}], expected [{S}, {plen}]")
+            self._check_aligned(t, f"fragment {i}", rstride if s > 1 else 0)
             S, plen, dev = s, l, t.device
             bases[i] = t.data_ptr()
             strides[i] = rstride
@@ -400,6 +415,7 @@ class ReedSolomon:
             if tuple(out.shape) != (S, oc, plen):
                 raise ValueError(f"out must be [S={S}, oc={oc}, L={plen}], "
                                  f"got {tuple(out.shape)}")
+            self._check_aligned(out, "out")
             outs = out
         else:
             outs = torch.empty((S, oc, plen), dtype=torch.uint8, device=dev)

@@ -281,3 +281,75 @@ def test_argument_checks(rs_mod):
     rs.sync()
     torch.cuda.synchronize()
     assert bool((out == 0xA5).all()), "a refused call wrote to the output"
+
+
+def test_alignment_checks(rs_mod):
+    """A nonzero source or destination address that is not 16-byte aligned
+    is refused on the host by the batch, multi-table and both plan entry
+    points: LIZEC_EINVAL, no plan returned, output untouched.  The Python
+    entry points raise ValueError naming the tensor."""
+    from lizardfs_amd import lib as L
+    from lizardfs_amd.ec import build_pattern_tables
+    k, m, S, plen = 8, 2, 4, 4096
+    rs = rs_mod(k, m)
+    lib, eng = L.lib(), L.engine(0)
+    tables, index, _ = build_pattern_tables(k, m, [{0, 1}, {2, 3}] * 2)
+    src_t = torch.zeros((S * k * plen + 64,), dtype=torch.uint8,
+                        device="cuda")
+    out = torch.full((S * m * plen + 64,), 0xA5, dtype=torch.uint8,
+                     device="cuda")
+    assert src_t.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0
+    src = src_t.data_ptr() + np.arange(S * k, dtype=np.uint64) * np.uint64(plen)
+    dst = out.data_ptr() + np.arange(S * m, dtype=np.uint64) * np.uint64(plen)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+
+    def call(src, dst):
+        src = np.ascontiguousarray(src, np.uint64)
+        dst = np.ascontiguousarray(dst, np.uint64)
+        tail = (src.ctypes.data_as(u64p), dst.ctypes.data_as(u64p), S)
+        one = (eng, plen, k, m, tables[0].ctypes.data_as(u8p)) + tail
+        multi = (eng, plen, k, m, tables.ctypes.data_as(u8p),
+                 tables.shape[0], index.ctypes.data_as(u32p)) + tail
+        plan, mplan = ctypes.c_void_p(), ctypes.c_void_p()
+        rcs = (lib.lizec_ec_encode_batch(*one, stream),
+               lib.lizec_ec_plan_create(*one, ctypes.byref(plan)),
+               lib.lizec_ec_encode_batch_multi(*multi, stream),
+               lib.lizec_ec_plan_create_multi(*multi, ctypes.byref(mplan)))
+        assert not plan.value and not mplan.value
+        return rcs
+
+    refused = (LIZEC_EINVAL,) * 4
+    for off in (1, 4, 8):
+        for at in (0, S * k - 1):          # first and last source
+            bad = src.copy()
+            bad[at] += np.uint64(off)
+            assert call(bad, dst) == refused, ("src", at, off)
+        for at in (0, S * m - 1):
+            bad = dst.copy()
+            bad[at] += np.uint64(off)
+            assert call(src, bad) == refused, ("dst", at, off)
+    rs.sync()
+    torch.cuda.synchronize()
+    assert bool((out == 0xA5).all()), "a refused call wrote to the output"
+
+    # the wrappers name the misaligned tensor
+    data = src_t[8:8 + S * k * plen].view(S, k, plen)
+    with pytest.raises(ValueError, match="data.*16-byte aligned"):
+        rs.encode_batch(data)
+    good = src_t[:S * k * plen].view(S, k, plen)
+    parity = out[4:4 + S * m * plen].view(S, m, plen)
+    with pytest.raises(ValueError, match="parity.*16-byte aligned"):
+        rs.encode_batch(good, parity)
+    frags = [None, None] + [good[:, i, :] for i in range(2, k)] + \
+        [src_t[8:8 + S * plen].view(S, plen), good[:, 0, :]]
+    with pytest.raises(ValueError, match="fragment 8.*16-byte aligned"):
+        rs.recover_batch(frags, erased=(0, 1))
+    mixed = [good[:, i, :] for i in range(k)] + \
+        [good[:, 0, :], src_t[8:8 + S * plen].view(S, plen)]
+    with pytest.raises(ValueError, match="fragment 9.*16-byte aligned"):
+        rs.recover_batch_mixed(mixed, [{0, 1}] * S)
+    torch.cuda.synchronize()
+    assert bool((out == 0xA5).all())
