@@ -227,6 +227,36 @@ int lizec_ec_plan_create_multi(lizec_engine *e, uint64_t part_len, int srcs,
                                const uint64_t *dst_dptrs, int num_stripes,
                                lizec_plan **out);
 
+/* Batched EC encode/decode over parts stored as 64 KiB blocks at a fixed
+ * stride, at addresses that need only be 4-byte aligned — the layout of an
+ * INTERLEAVED-format chunk part (kHddBlockSize = 65540, chunk.h:40: block
+ * b's data at 4 + 65540*b, so its alignment cycles through 4, 8, 12, 0
+ * mod 16).  Survivors can be read from such images and parts rebuilt into
+ * them in place.
+ *  nblocks  : 64 KiB blocks per part (part length = nblocks*65536 <= 2^31)
+ *  gftbls, src_dptrs, dst_dptrs, num_stripes: as for lizec_ec_encode_batch,
+ *             an address being that of block 0's DATA (the caller folds a
+ *             header, or an image's leading 4 bytes, into it)
+ *  src_block_stride / dst_block_stride: block b of a part lies at
+ *             address + b*stride; >= 65536, one value per side
+ * Only bytes inside [block, block + 65536) are read or written: whatever
+ * lies between two destination blocks (the CRC slots) survives the call.
+ * Returns LIZEC_EINVAL from the host, with nothing enqueued, if an address
+ * or stride is not a multiple of 4, a stride is below 65536, nblocks is 0
+ * or nblocks*65536 > 2^31, srcs or dests is outside 1..32, an address is 0,
+ * or num_stripes*nblocks*8 (the batch counted in 8 KiB tiles, one
+ * workgroup each) exceeds 2^31-1.
+ * A side whose addresses and stride are all multiples of 16 keeps the
+ * aligned vector accesses; with both sides so and both strides 65536 the
+ * call is lizec_ec_encode_batch at part_len = nblocks*65536.  Stream and
+ * thread contract as for the other batch calls. */
+int lizec_ec_encode_batch_strided(lizec_engine *e, uint32_t nblocks, int srcs,
+                                  int dests, const uint8_t *gftbls,
+                                  const uint64_t *src_dptrs,
+                                  const uint64_t *dst_dptrs, int num_stripes,
+                                  uint32_t src_block_stride,
+                                  uint32_t dst_block_stride, void *stream);
+
 /* Per-block CRC32 over a contiguous device buffer:
  *  dev_crcs_out[b] = lizec_crc32(seed, dev_buf + b*block_len, block_len)
  * The chunkserver's per-64KiB-block gate (hddspacemgr.cc:1918-1920, scrub
@@ -270,6 +300,20 @@ int lizec_scrub_batch_strided(lizec_engine *e, const uint64_t *chunk_dptrs,
                               uint32_t block_stride, uint32_t crc_stride,
                               int32_t *dev_status_out, void *stream);
 
+/* The store counterpart of lizec_scrub_batch_strided: computes the CRC of
+ * every 64 KiB block (at data_offs[i] + b*block_stride) and STORES it
+ * big-endian at crc_offs[i] + b*crc_stride; no other byte of an image is
+ * written.  Arguments as above, without the status array.  Block data must
+ * be 4-byte aligned (chunk_dptrs[i] + data_offs[i] and block_stride
+ * multiples of 4) and block_stride >= 65536; anything else, an address of
+ * 0, or no blocks at all returns LIZEC_EINVAL with nothing enqueued. */
+int lizec_crc_fill_batch_strided(lizec_engine *e, const uint64_t *chunk_dptrs,
+                                 const uint32_t *data_offs,
+                                 const uint32_t *crc_offs,
+                                 const uint32_t *block_counts, int nchunks,
+                                 uint32_t block_stride, uint32_t crc_stride,
+                                 void *stream);
+
 /* Pinned host memory for the streaming APIs (hipHostMalloc/hipHostFree):
  * pageable buffers work too but degrade the pipeline to synchronous
  * copies. */
@@ -296,6 +340,19 @@ int lizec_replicate_run(lizec_engine *e, uint64_t part_len, int ic, int oc,
                         const uint8_t *sigs, uint32_t sig_len,
                         uint32_t header_size, uint32_t crc_off,
                         const uint64_t *host_dst, int nchunks, int sub_batch);
+
+/* The same pipeline emitting INTERLEAVED-format images (chunk.cc:191-209),
+ * for a chunkserver that does not create chunks in MooseFS format: no
+ * header and no signature; block b's big-endian CRC at 65540*b and its
+ * data right behind it.  Recovery writes straight into the images through
+ * the strided EC kernel.
+ *  host_dst : nchunks*oc HOST addresses, (part_len/65536)*65540 bytes each
+ * Everything else as for lizec_replicate_run. */
+int lizec_replicate_run_interleaved(lizec_engine *e, uint64_t part_len, int ic,
+                                    int oc, const uint8_t *gftbls,
+                                    const uint64_t *host_src,
+                                    const uint64_t *host_dst, int nchunks,
+                                    int sub_batch);
 
 #ifdef __cplusplus
 }

@@ -40,6 +40,7 @@
 
 #include "ec_kernel.h"
 #include "ec_kernel_multi.h"
+#include "ec_kernel_strided.h"
 #include "crc_fold.h"
 
 /* Product kernel configuration (chosen by the variant A/B harness,
@@ -678,6 +679,38 @@ static int run_batch(uint64_t part_len, int srcs, int dests,
 	return LIZEC_OK;
 }
 
+/* Upload one table and the two pointer arrays of a single-table batch
+ * through the stream's scratch; on success *d_src / *d_dst are the device
+ * pointer arrays and c->d_gftbls the packed table. */
+static int upload_single_table(lizec_engine *e, hipStream_t s, int srcs,
+                               int dests, const uint8_t *gftbls,
+                               const uint64_t *src_dptrs, size_t nsrc,
+                               const uint64_t *dst_dptrs, size_t ndst,
+                               lizec_stream_ctx **ctx, uint64_t **d_src,
+                               uint64_t **d_dst) {
+	lizec_stream_ctx *c;
+	int r = ctx_acquire(e, s, nsrc + ndst, (nsrc + ndst) * 8, &c);
+	if (r != LIZEC_OK) return r;
+	*ctx = c;
+	*d_src = c->d_ptrs;
+	*d_dst = c->d_ptrs + nsrc;
+	/* stage tables + pointer arrays through this stream's pinned buffer
+	 * (ctx_acquire waited until any previous copies from it finished) */
+	uint8_t *tstage = c->h_staging;
+	uint64_t *pstage = (uint64_t *)(c->h_staging + (size_t)kECTblBytes * 32 * 32);
+	for (int i = 0; i < srcs * dests; ++i)
+		pack_mixed_radix(gftbls + (size_t)i * 32, tstage + (size_t)i * kECTblBytes);
+	memcpy(pstage, src_dptrs, nsrc * 8);
+	memcpy(pstage + nsrc, dst_dptrs, ndst * 8);
+	LIZEC_CHECK(hipMemcpyAsync(c->d_gftbls, tstage, (size_t)kECTblBytes * srcs * dests,
+	                           hipMemcpyHostToDevice, s));
+	LIZEC_CHECK(hipMemcpyAsync(*d_src, pstage, (nsrc + ndst) * 8,
+	                           hipMemcpyHostToDevice, s));
+	LIZEC_CHECK(hipEventRecord(c->uploaded, s));
+	c->ev_recorded = true;
+	return LIZEC_OK;
+}
+
 extern "C" int lizec_ec_encode_batch(lizec_engine *e, uint64_t part_len,
                                      int srcs, int dests,
                                      const uint8_t *gftbls,
@@ -695,27 +728,126 @@ extern "C" int lizec_ec_encode_batch(lizec_engine *e, uint64_t part_len,
 	LIZEC_CHECK(hipSetDevice(e->device));
 
 	lizec_stream_ctx *c;
-	r = ctx_acquire(e, s, nsrc + ndst, (nsrc + ndst) * 8, &c);
+	uint64_t *d_src, *d_dst;
+	r = upload_single_table(e, s, srcs, dests, gftbls, src_dptrs, nsrc,
+	                        dst_dptrs, ndst, &c, &d_src, &d_dst);
 	if (r != LIZEC_OK) return r;
-	uint64_t *d_src = c->d_ptrs;
-	uint64_t *d_dst = c->d_ptrs + nsrc;
-	/* stage tables + pointer arrays through this stream's pinned buffer
-	 * (ctx_acquire waited until any previous copies from it finished) */
-	uint8_t *tstage = c->h_staging;
-	uint64_t *pstage = (uint64_t *)(c->h_staging + (size_t)kECTblBytes * 32 * 32);
-	for (int i = 0; i < srcs * dests; ++i)
-		pack_mixed_radix(gftbls + (size_t)i * 32, tstage + (size_t)i * kECTblBytes);
-	memcpy(pstage, src_dptrs, nsrc * 8);
-	memcpy(pstage + nsrc, dst_dptrs, ndst * 8);
-	LIZEC_CHECK(hipMemcpyAsync(c->d_gftbls, tstage, (size_t)kECTblBytes * srcs * dests,
-	                           hipMemcpyHostToDevice, s));
-	LIZEC_CHECK(hipMemcpyAsync(d_src, pstage, (nsrc + ndst) * 8,
-	                           hipMemcpyHostToDevice, s));
-	LIZEC_CHECK(hipEventRecord(c->uploaded, s));
-	c->ev_recorded = true;
-
 	return run_batch(part_len, srcs, dests, c->d_gftbls, d_src, d_dst,
 	                 (uint32_t)num_stripes, s);
+}
+
+/* ------------------------------------------------------------------ */
+/* Block-strided, 4-byte-aligned parts (ec_kernel_strided.h)          */
+/* ------------------------------------------------------------------ */
+
+/* One pass of the strided kernel: exactly one workgroup per tile. */
+template <int D>
+static void launch_ec_strided(uint32_t nblocks, int srcs, int dest_base,
+                              const uint8_t *d_tbls, const uint64_t *d_src,
+                              const uint64_t *d_dst, int dests_total,
+                              uint32_t nstripes, uint32_t src_stride,
+                              uint32_t dst_stride, bool sal, bool dal,
+                              hipStream_t s) {
+	constexpr int CH = ec_chunks_for(D);
+	uint32_t tiles_per_part = nblocks * (kECBlockBytes / (kChunkBytes * CH));
+	uint32_t total_tiles = tiles_per_part * nstripes;
+	size_t lds = (size_t)D * srcs * kECTblBytes;
+#define LIZEC_LAUNCH_STRIDED(SAL, DAL)                                      \
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(ec_encode_strided_kernel<D, CH, SAL, DAL>), \
+	                   dim3(total_tiles), dim3(kThreads), lds, s,           \
+	                   tiles_per_part, srcs, dest_base, d_tbls, d_src,      \
+	                   d_dst, dests_total, src_stride, dst_stride)
+	if (sal && dal) LIZEC_LAUNCH_STRIDED(true, true);
+	else if (sal) LIZEC_LAUNCH_STRIDED(true, false);
+	else if (dal) LIZEC_LAUNCH_STRIDED(false, true);
+	else LIZEC_LAUNCH_STRIDED(false, false);
+#undef LIZEC_LAUNCH_STRIDED
+}
+
+/* Largest batch of the strided kernel, counted in 8 KiB tiles (the smaller
+ * of the two tile sizes): the grid is one workgroup per tile. */
+static bool strided_tiles_fit(uint32_t nblocks, uint32_t num_stripes) {
+	return (uint64_t)nblocks * (kECBlockBytes / (kChunkBytes * 2)) *
+	           num_stripes <= 0x7FFFFFFFull;
+}
+
+/* run_batch for strided parts: the same split into passes of at most 8
+ * destinations.  sal / dal: that side is 16-byte aligned throughout. */
+static int run_batch_strided(uint32_t nblocks, int srcs, int dests,
+                             const uint8_t *d_tbls, const uint64_t *d_src,
+                             const uint64_t *d_dst, uint32_t num_stripes,
+                             uint32_t src_stride, uint32_t dst_stride,
+                             bool sal, bool dal, hipStream_t s) {
+	if (!strided_tiles_fit(nblocks, num_stripes)) return LIZEC_EINVAL;
+	for (int base = 0; base < dests;) {
+		int d = dests - base;
+		if (d > 8) d = 8;
+#define LIZEC_LAUNCH_STRIDED_D(D)                                          \
+	launch_ec_strided<D>(nblocks, srcs, base, d_tbls, d_src, d_dst, dests, \
+	                     num_stripes, src_stride, dst_stride, sal, dal, s)
+		switch (d) {
+		case 1: LIZEC_LAUNCH_STRIDED_D(1); break;
+		case 2: LIZEC_LAUNCH_STRIDED_D(2); break;
+		case 3: LIZEC_LAUNCH_STRIDED_D(3); break;
+		case 4: LIZEC_LAUNCH_STRIDED_D(4); break;
+		case 5: LIZEC_LAUNCH_STRIDED_D(5); break;
+		case 6: LIZEC_LAUNCH_STRIDED_D(6); break;
+		case 7: LIZEC_LAUNCH_STRIDED_D(7); break;
+		default: LIZEC_LAUNCH_STRIDED_D(8); break;
+		}
+#undef LIZEC_LAUNCH_STRIDED_D
+		base += d;
+	}
+	LIZEC_CHECK(hipGetLastError());
+	return LIZEC_OK;
+}
+
+extern "C" int lizec_ec_encode_batch_strided(
+    lizec_engine *e, uint32_t nblocks, int srcs, int dests,
+    const uint8_t *gftbls, const uint64_t *src_dptrs,
+    const uint64_t *dst_dptrs, int num_stripes, uint32_t src_block_stride,
+    uint32_t dst_block_stride, void *stream) {
+	if (!e || !gftbls || !src_dptrs || !dst_dptrs) return LIZEC_EINVAL;
+	if (srcs < 1 || srcs > 32 || dests < 1 || dests > 32 || num_stripes < 1)
+		return LIZEC_EINVAL;
+	if (nblocks == 0 || (uint64_t)nblocks * kECBlockBytes > (uint64_t)1 << 31)
+		return LIZEC_EINVAL;
+	if (src_block_stride < kECBlockBytes || dst_block_stride < kECBlockBytes)
+		return LIZEC_EINVAL;
+	if (!strided_tiles_fit(nblocks, (uint32_t)num_stripes))
+		return LIZEC_EINVAL;
+	size_t nsrc = (size_t)num_stripes * srcs;
+	size_t ndst = (size_t)num_stripes * dests;
+	/* every address nonzero; per side, the OR of addresses and stride
+	 * decides between refusal (not 4-byte aligned), the dword-aligned
+	 * kernel forms, and the 16-byte-aligned ones */
+	uint64_t sbits = src_block_stride, dbits = dst_block_stride;
+	for (size_t i = 0; i < nsrc; ++i) {
+		if (!src_dptrs[i]) return LIZEC_EINVAL;
+		sbits |= src_dptrs[i];
+	}
+	for (size_t i = 0; i < ndst; ++i) {
+		if (!dst_dptrs[i]) return LIZEC_EINVAL;
+		dbits |= dst_dptrs[i];
+	}
+	if ((sbits | dbits) & 3) return LIZEC_EINVAL;
+	const bool sal = (sbits & 15) == 0, dal = (dbits & 15) == 0;
+	hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+	LIZEC_CHECK(hipSetDevice(e->device));
+
+	lizec_stream_ctx *c;
+	uint64_t *d_src, *d_dst;
+	int r = upload_single_table(e, s, srcs, dests, gftbls, src_dptrs, nsrc,
+	                            dst_dptrs, ndst, &c, &d_src, &d_dst);
+	if (r != LIZEC_OK) return r;
+	/* contiguous, fully aligned parts are the uniform kernel's case */
+	if (sal && dal && src_block_stride == kECBlockBytes &&
+	    dst_block_stride == kECBlockBytes)
+		return run_batch((uint64_t)nblocks * kECBlockBytes, srcs, dests,
+		                 c->d_gftbls, d_src, d_dst, (uint32_t)num_stripes, s);
+	return run_batch_strided(nblocks, srcs, dests, c->d_gftbls, d_src, d_dst,
+	                         (uint32_t)num_stripes, src_block_stride,
+	                         dst_block_stride, sal, dal, s);
 }
 
 /* Multi-table launch: same grid/tile/LDS shape as launch_ec. */
@@ -1135,6 +1267,37 @@ extern "C" int lizec_crc32_batch(lizec_engine *e, const void *dev_buf,
 	return LIZEC_OK;
 }
 
+/* Upload the per-image tables of a scrub / CRC-fill call into the stream's
+ * scratch (u64 slots reused): [dptrs u64 x n][doffs u32 x n][coffs][counts] */
+static int upload_image_meta(lizec_engine *e, hipStream_t s,
+                             const uint64_t *chunk_dptrs,
+                             const uint32_t *data_offs,
+                             const uint32_t *crc_offs,
+                             const uint32_t *block_counts, int nchunks,
+                             uint64_t **d_ptrs, uint32_t **d_doffs,
+                             uint32_t **d_coffs, uint32_t **d_counts) {
+	size_t words = (size_t)nchunks;               /* dptrs */
+	size_t meta = words + (3 * words * 4 + 7) / 8;
+	size_t bytes = meta * 8;
+	lizec_stream_ctx *c;
+	int r = ctx_acquire(e, s, meta + 8, bytes, &c);
+	if (r != LIZEC_OK) return r;
+	*d_ptrs = c->d_ptrs;
+	*d_doffs = (uint32_t *)(c->d_ptrs + nchunks);
+	*d_coffs = *d_doffs + nchunks;
+	*d_counts = *d_coffs + nchunks;
+	uint8_t *st = c->h_staging + (size_t)kECTblBytes * 32 * 32;
+	memcpy(st, chunk_dptrs, (size_t)nchunks * 8);
+	memcpy(st + (size_t)nchunks * 8, data_offs, (size_t)nchunks * 4);
+	memcpy(st + (size_t)nchunks * 12, crc_offs, (size_t)nchunks * 4);
+	memcpy(st + (size_t)nchunks * 16, block_counts, (size_t)nchunks * 4);
+	LIZEC_CHECK(hipMemcpyAsync(c->d_ptrs, st, (size_t)nchunks * 20,
+	                           hipMemcpyHostToDevice, s));
+	LIZEC_CHECK(hipEventRecord(c->uploaded, s));
+	c->ev_recorded = true;
+	return LIZEC_OK;
+}
+
 extern "C" int lizec_scrub_batch_strided(
     lizec_engine *e, const uint64_t *chunk_dptrs, const uint32_t *data_offs,
     const uint32_t *crc_offs, const uint32_t *block_counts, int nchunks,
@@ -1144,27 +1307,12 @@ extern "C" int lizec_scrub_batch_strided(
 		return LIZEC_EINVAL;
 	hipStream_t s = stream ? (hipStream_t)stream : e->stream;
 	LIZEC_CHECK(hipSetDevice(e->device));
-	/* upload per-chunk tables into stream scratch (u64 slots reused):
-	 * [dptrs u64 x n][doffs u32 x n][coffs][counts] */
-	size_t words = (size_t)nchunks;               /* dptrs */
-	size_t meta = words + (3 * words * 4 + 7) / 8;
-	size_t bytes = meta * 8;
-	lizec_stream_ctx *c;
-	int r = ctx_acquire(e, s, meta + 8, bytes, &c);
+	uint64_t *d_ptrs;
+	uint32_t *d_doffs, *d_coffs, *d_counts;
+	int r = upload_image_meta(e, s, chunk_dptrs, data_offs, crc_offs,
+	                          block_counts, nchunks, &d_ptrs, &d_doffs,
+	                          &d_coffs, &d_counts);
 	if (r != LIZEC_OK) return r;
-	uint64_t *d_ptrs = c->d_ptrs;
-	uint32_t *d_doffs = (uint32_t *)(d_ptrs + nchunks);
-	uint32_t *d_coffs = d_doffs + nchunks;
-	uint32_t *d_counts = d_coffs + nchunks;
-	uint8_t *st = c->h_staging + (size_t)kECTblBytes * 32 * 32;
-	memcpy(st, chunk_dptrs, (size_t)nchunks * 8);
-	memcpy(st + (size_t)nchunks * 8, data_offs, (size_t)nchunks * 4);
-	memcpy(st + (size_t)nchunks * 12, crc_offs, (size_t)nchunks * 4);
-	memcpy(st + (size_t)nchunks * 16, block_counts, (size_t)nchunks * 4);
-	LIZEC_CHECK(hipMemcpyAsync(d_ptrs, st, (size_t)nchunks * 20,
-	                           hipMemcpyHostToDevice, s));
-	LIZEC_CHECK(hipEventRecord(c->uploaded, s));
-	c->ev_recorded = true;
 	uint32_t max_blocks = 0;
 	for (int i = 0; i < nchunks; ++i)
 		if (block_counts[i] > max_blocks) max_blocks = block_counts[i];
@@ -1189,16 +1337,51 @@ extern "C" int lizec_scrub_batch_strided(
 static int image_crc_launch(lizec_engine *e, const uint64_t *d_ptrs,
                             const uint32_t *d_doffs, const uint32_t *d_coffs,
                             const uint32_t *d_counts, int nimages,
-                            uint32_t max_blocks, hipStream_t s) {
+                            uint32_t max_blocks, uint32_t block_stride,
+                            uint32_t crc_stride, hipStream_t s) {
 	uint64_t total = (uint64_t)nimages * max_blocks;
 	uint64_t groups = (total + 3) / 4;
 	uint32_t grid = (uint32_t)(groups < 131072 ? groups : 131072);
 	hipLaunchKernelGGL(HIP_KERNEL_NAME(scrub_chunks_kernel<true>),
 	                   dim3(grid), dim3(kThreads), 0, s, d_ptrs, d_doffs,
 	                   d_coffs, d_counts, (uint32_t)nimages, max_blocks,
-	                   65536u, 4u, e->d_crc_const, nullptr);
+	                   block_stride, crc_stride, e->d_crc_const, nullptr);
 	LIZEC_CHECK(hipGetLastError());
 	return LIZEC_OK;
+}
+
+/* The store counterpart of lizec_scrub_batch_strided: compute every block's
+ * CRC and write it big-endian into the image. */
+extern "C" int lizec_crc_fill_batch_strided(
+    lizec_engine *e, const uint64_t *chunk_dptrs, const uint32_t *data_offs,
+    const uint32_t *crc_offs, const uint32_t *block_counts, int nchunks,
+    uint32_t block_stride, uint32_t crc_stride, void *stream) {
+	if (!e || !chunk_dptrs || !data_offs || !crc_offs || !block_counts ||
+	    nchunks < 1)
+		return LIZEC_EINVAL;
+	/* blocks are read in 32-bit words or wider, and must not overlap */
+	if (block_stride < 65536u || (block_stride & 3)) return LIZEC_EINVAL;
+	uint32_t max_blocks = 0;
+	for (int i = 0; i < nchunks; ++i) {
+		if (!chunk_dptrs[i] || ((chunk_dptrs[i] + data_offs[i]) & 3))
+			return LIZEC_EINVAL;
+		if (block_counts[i] > max_blocks) max_blocks = block_counts[i];
+	}
+	/* the kernel forms b*stride in 32 bits */
+	if (max_blocks == 0 ||
+	    (uint64_t)max_blocks * block_stride > 0xFFFFFFFFull ||
+	    (uint64_t)max_blocks * crc_stride > 0xFFFFFFFFull)
+		return LIZEC_EINVAL;
+	hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+	LIZEC_CHECK(hipSetDevice(e->device));
+	uint64_t *d_ptrs;
+	uint32_t *d_doffs, *d_coffs, *d_counts;
+	int r = upload_image_meta(e, s, chunk_dptrs, data_offs, crc_offs,
+	                          block_counts, nchunks, &d_ptrs, &d_doffs,
+	                          &d_coffs, &d_counts);
+	if (r != LIZEC_OK) return r;
+	return image_crc_launch(e, d_ptrs, d_doffs, d_coffs, d_counts, nchunks,
+	                        max_blocks, block_stride, crc_stride, s);
 }
 
 /* MooseFS layout: 64 KiB blocks after the header, 4-byte CRC array. */
@@ -1247,6 +1430,16 @@ static void repl_slot_free(repl_slot &sl) {
 	sl = repl_slot();
 }
 
+/* Where an emitted image keeps its blocks and CRCs. */
+struct repl_layout {
+	uint64_t img_bytes;
+	uint32_t header_size;    /* zero-filled, then signed; 0 = no header */
+	uint32_t data_off;       /* block 0's data */
+	uint32_t crc_off;        /* block 0's CRC */
+	uint32_t block_stride;
+	uint32_t crc_stride;
+};
+
 /* The ChunkReplicator::replicate loop (chunk_replicator.cc:139-196) as a
  * host-to-host streaming pipeline: pull surviving parts from host memory
  * (the reference pulls them from peer sockets), recover the erased parts
@@ -1261,24 +1454,21 @@ static void repl_slot_free(repl_slot &sl) {
  * gftbls:    32*ic*oc recover tables (lizec_rs_tables)
  * sigs:      nchunks*oc signatures, sig_len bytes each
  * host_dst:  nchunks*oc host addresses (header_size + part_len each)
- * sub_batch: chunks per pipeline stage (0 = auto) */
-extern "C" int lizec_replicate_run(lizec_engine *e, uint64_t part_len,
-                                   int ic, int oc, const uint8_t *gftbls,
-                                   const uint64_t *host_src,
-                                   const uint8_t *sigs, uint32_t sig_len,
-                                   uint32_t header_size, uint32_t crc_off,
-                                   const uint64_t *host_dst, int nchunks,
-                                   int sub_batch) {
-	if (!e || !gftbls || !host_src || !host_dst || nchunks < 1)
-		return LIZEC_EINVAL;
-	if (ic < 1 || ic > 32 || oc < 1 || oc > 32) return LIZEC_EINVAL;
-	if (part_len == 0 || part_len % 65536 || part_len > (uint64_t)1 << 31)
-		return LIZEC_EINVAL;
-	if (sig_len > header_size || crc_off + 4 * (part_len / 65536) > header_size)
-		return LIZEC_EINVAL;
+ * sub_batch: chunks per pipeline stage (0 = auto)
+ *
+ * This is the body of both entry points, lizec_replicate_run (MooseFS
+ * images, as described) and lizec_replicate_run_interleaved; they differ
+ * only in `lay`, and have checked e, part_len, ic and oc. */
+static int replicate_run_impl(lizec_engine *e, uint64_t part_len, int ic,
+                              int oc, const uint8_t *gftbls,
+                              const uint64_t *host_src, const uint8_t *sigs,
+                              uint32_t sig_len, const repl_layout &lay,
+                              const uint64_t *host_dst, int nchunks,
+                              int sub_batch) {
 	LIZEC_CHECK(hipSetDevice(e->device));
 
-	const uint64_t img_bytes = header_size + part_len;
+	const uint64_t img_bytes = lay.img_bytes;
+	const uint32_t header_size = lay.header_size;
 	int B = sub_batch;
 	if (B <= 0) {
 		/* ~2 GiB of device staging per slot (sub_batch 16 at ec(8,2)
@@ -1354,9 +1544,9 @@ extern "C" int lizec_replicate_run(lizec_engine *e, uint64_t part_len,
 				size_t n = (size_t)i * oc + j;
 				uint64_t img = (uint64_t)(s.d_img + n * img_bytes);
 				h_img[n] = img;
-				h_dst[n] = img + header_size;
-				h_off[n] = header_size;
-				h_coff[n] = crc_off;
+				h_dst[n] = img + lay.data_off;
+				h_off[n] = lay.data_off;
+				h_coff[n] = lay.crc_off;
 				h_cnt[n] = nblocks;
 			}
 		if (sigs)
@@ -1377,7 +1567,7 @@ extern "C" int lizec_replicate_run(lizec_engine *e, uint64_t part_len,
 			rc = LIZEC_EHIP;
 			break;
 		}
-		for (int n = 0; n < nb * oc && rc == LIZEC_OK; ++n) {
+		for (int n = 0; header_size && n < nb * oc && rc == LIZEC_OK; ++n) {
 			uint8_t *img = s.d_img + (size_t)n * img_bytes;
 			if (hipMemsetAsync(img, 0, header_size, st) != hipSuccess)
 				rc = LIZEC_EHIP;
@@ -1393,11 +1583,19 @@ extern "C" int lizec_replicate_run(lizec_engine *e, uint64_t part_len,
 		uint32_t *d_off = (uint32_t *)(d_img_ptrs + n_dst);
 		uint32_t *d_coff = d_off + n_dst;
 		uint32_t *d_cnt = d_coff + n_dst;
-		rc = run_batch(part_len, ic, oc, d_tbl, d_src, d_dst, (uint32_t)nb,
-		               st);
+		if (lay.block_stride == kECBlockBytes)
+			rc = run_batch(part_len, ic, oc, d_tbl, d_src, d_dst,
+			               (uint32_t)nb, st);
+		else
+			/* staged sources are contiguous and aligned; the images are
+			 * packed at n*img_bytes, so their blocks start at every
+			 * 4-byte phase */
+			rc = run_batch_strided(nblocks, ic, oc, d_tbl, d_src, d_dst,
+			                       (uint32_t)nb, kECBlockBytes,
+			                       lay.block_stride, true, false, st);
 		if (rc != LIZEC_OK) break;
 		rc = image_crc_launch(e, d_img_ptrs, d_off, d_coff, d_cnt, nb * oc,
-		                      nblocks, st);
+		                      nblocks, lay.block_stride, lay.crc_stride, st);
 		if (rc != LIZEC_OK) break;
 		for (int n = 0; n < nb * oc && rc == LIZEC_OK; ++n)
 			if (hipMemcpyAsync((void *)host_dst[(size_t)c0 * oc + n],
@@ -1414,4 +1612,51 @@ extern "C" int lizec_replicate_run(lizec_engine *e, uint64_t part_len,
 	}
 	(void)hipFree(d_tbl);
 	return rc;
+}
+
+static int check_replicate_args(lizec_engine *e, uint64_t part_len, int ic,
+                                int oc, const uint8_t *gftbls,
+                                const uint64_t *host_src,
+                                const uint64_t *host_dst, int nchunks) {
+	if (!e || !gftbls || !host_src || !host_dst || nchunks < 1)
+		return LIZEC_EINVAL;
+	if (ic < 1 || ic > 32 || oc < 1 || oc > 32) return LIZEC_EINVAL;
+	if (part_len == 0 || part_len % 65536 || part_len > (uint64_t)1 << 31)
+		return LIZEC_EINVAL;
+	return LIZEC_OK;
+}
+
+extern "C" int lizec_replicate_run(lizec_engine *e, uint64_t part_len,
+                                   int ic, int oc, const uint8_t *gftbls,
+                                   const uint64_t *host_src,
+                                   const uint8_t *sigs, uint32_t sig_len,
+                                   uint32_t header_size, uint32_t crc_off,
+                                   const uint64_t *host_dst, int nchunks,
+                                   int sub_batch) {
+	int r = check_replicate_args(e, part_len, ic, oc, gftbls, host_src,
+	                             host_dst, nchunks);
+	if (r != LIZEC_OK) return r;
+	if (sig_len > header_size || crc_off + 4 * (part_len / 65536) > header_size)
+		return LIZEC_EINVAL;
+	const repl_layout lay = {header_size + part_len, header_size, header_size,
+	                         crc_off, kECBlockBytes, 4u};
+	return replicate_run_impl(e, part_len, ic, oc, gftbls, host_src, sigs,
+	                          sig_len, lay, host_dst, nchunks, sub_batch);
+}
+
+/* The same pipeline emitting INTERLEAVED-format images (chunk.cc:191-209):
+ * no header and no signature; block b's big-endian CRC at 65540*b, its data
+ * right behind it. */
+extern "C" int lizec_replicate_run_interleaved(
+    lizec_engine *e, uint64_t part_len, int ic, int oc, const uint8_t *gftbls,
+    const uint64_t *host_src, const uint64_t *host_dst, int nchunks,
+    int sub_batch) {
+	int r = check_replicate_args(e, part_len, ic, oc, gftbls, host_src,
+	                             host_dst, nchunks);
+	if (r != LIZEC_OK) return r;
+	constexpr uint32_t kHddBlock = kECBlockBytes + 4;   /* chunk.h:40 */
+	const repl_layout lay = {part_len / kECBlockBytes * kHddBlock, 0u, 4u, 0u,
+	                         kHddBlock, kHddBlock};
+	return replicate_run_impl(e, part_len, ic, oc, gftbls, host_src, nullptr,
+	                          0u, lay, host_dst, nchunks, sub_batch);
 }

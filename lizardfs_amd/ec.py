@@ -19,6 +19,9 @@ from . import lib as L
 from . import slice_traits
 
 
+_BLOCK = slice_traits.BLOCK_SIZE   # 64 KiB
+
+
 def _tables_cache_key(k, m, present, nonnull, needed):
     return (k, m, present, nonnull, needed)
 
@@ -367,6 +370,105 @@ class ReedSolomon:
                         S, plen)
         self._run(plen, tbl, ic, oc, np.ascontiguousarray(src.ravel()),
                   np.ascontiguousarray(dst.ravel()), S, plan_key=plan_key)
+        return outs
+
+    def recover_batch_blocks(self, fragments, erased, want=None, out=None, *,
+                             nblocks, src_stride=_BLOCK, dst_stride=_BLOCK):
+        """recover_batch over parts stored as 64 KiB blocks at a fixed
+        stride, at addresses that need only be 4-byte aligned
+        (lizec_ec_encode_batch_strided) — survivors read straight from
+        INTERLEAVED-format images, parts rebuilt straight into them.
+
+        fragments, erased, want: as for recover_batch, except that a
+          fragment is a [S, span] row view starting at block 0's DATA (for
+          an INTERLEAVED image batch, img[:, 4:]); block b of row s lies at
+          byte b*src_stride of the row, span >= (nblocks-1)*src_stride +
+          65536.  Encode is the case erased = want = the parity parts.
+        out: dict part -> [S, span] row view laid out the same way with
+          dst_stride; required unless dst_stride is 65536, where plain
+          [S, nblocks*65536] tensors are allocated.  Only the blocks are
+          written: bytes between them (the CRC slots) keep their value.
+        Rows and strides must be multiples of 4 bytes.
+        Returns dict part_index -> tensor.
+        """
+        nparts = self.k + self.m
+        if len(fragments) != nparts:
+            raise ValueError(f"need {nparts} fragment slots")
+        erased = frozenset(erased)
+        if len(erased) != self.m:
+            raise ValueError(f"exactly m={self.m} erased parts required "
+                             f"(got {len(erased)}); pad like ec_read_plan.h:126")
+        want = frozenset(want) if want is not None else erased
+        if not want.issubset(erased):
+            raise ValueError("want must be a subset of erased")
+        nblocks = int(nblocks)
+        if nblocks < 1 or nblocks * _BLOCK > 1 << 31:
+            raise ValueError(f"nblocks={nblocks} out of [1, 32768]")
+        for name, stride in (("src_stride", src_stride),
+                             ("dst_stride", dst_stride)):
+            if stride < _BLOCK or stride % 4:
+                raise ValueError(f"{name}={stride} must be a multiple of 4 "
+                                 f"and at least {_BLOCK}")
+        if out is None and dst_stride != _BLOCK:
+            raise ValueError("out is required when dst_stride != 65536")
+
+        def rows_of(t, what, stride):
+            """[S, span] view -> (S, row addresses), layout checked."""
+            s, span, rstride = self._frag_geom(t, what)
+            need = (nblocks - 1) * stride + _BLOCK
+            if span < need:
+                raise ValueError(f"{what}: rows of {span} bytes cannot hold "
+                                 f"{nblocks} blocks at stride {stride} "
+                                 f"({need} bytes)")
+            if t.data_ptr() % 4 or (s > 1 and rstride % 4):
+                raise ValueError(f"{what}: block data must be 4-byte aligned "
+                                 f"(address {t.data_ptr():#x}, row stride "
+                                 f"{rstride})")
+            return s, (t.data_ptr() +
+                       np.arange(s, dtype=np.uint64) * np.uint64(rstride))
+
+        present = nonnull = needed = 0
+        S = dev = None
+        src_cols = []
+        for i in range(nparts):
+            if i in erased:
+                continue
+            present |= 1 << i
+            if fragments[i] is not None:
+                s, rows = rows_of(fragments[i], f"fragment {i}", src_stride)
+                if S is not None and s != S:
+                    raise ValueError(f"fragment {i} has {s} rows, "
+                                     f"expected {S}")
+                nonnull |= 1 << i
+                S, dev = s, fragments[i].device
+                src_cols.append(rows)
+        for i in want:
+            needed |= 1 << i
+        if S is None:
+            raise ValueError("all surviving parts are None")
+
+        tbl, ic, oc = self._get_tables(present, nonnull, needed)
+        if out is not None:
+            outs = out
+        else:
+            outs = {i: torch.empty((S, nblocks * _BLOCK), dtype=torch.uint8,
+                                   device=dev) for i in sorted(want)}
+        dst_cols = []
+        for i in sorted(want):
+            s, rows = rows_of(outs[i], f"out[{i}]", dst_stride)
+            if s != S:
+                raise ValueError(f"out[{i}] has {s} rows, expected {S}")
+            dst_cols.append(rows)
+        src = np.ascontiguousarray(np.stack(src_cols, axis=1).ravel())
+        dst = np.ascontiguousarray(np.stack(dst_cols, axis=1).ravel())
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        L.check(self._lib.lizec_ec_encode_batch_strided(
+            self._engine, nblocks, ic, oc,
+            tbl.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+            src.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+            dst.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+            S, src_stride, dst_stride, ctypes.c_void_p(stream)),
+            "lizec_ec_encode_batch_strided")
         return outs
 
     def recover_batch_mixed(self, fragments, erased, want=None, out=None):

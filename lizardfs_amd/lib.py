@@ -119,6 +119,22 @@ def lib():
         ctypes.POINTER(ctypes.c_uint64), u8p, ctypes.c_uint32,
         ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64),
         ctypes.c_int, ctypes.c_int]
+    L.lizec_ec_encode_batch_strided.restype = ctypes.c_int
+    L.lizec_ec_encode_batch_strided.argtypes = [
+        ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, u8p,
+        ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+        ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
+    L.lizec_crc_fill_batch_strided.restype = ctypes.c_int
+    L.lizec_crc_fill_batch_strided.argtypes = [
+        ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
+        ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+        ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, ctypes.c_uint32,
+        ctypes.c_uint32, ctypes.c_void_p]
+    L.lizec_replicate_run_interleaved.restype = ctypes.c_int
+    L.lizec_replicate_run_interleaved.argtypes = [
+        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, u8p,
+        ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+        ctypes.c_int, ctypes.c_int]
     _lib = L
     return _lib
 

@@ -20,22 +20,63 @@ from . import slice_traits as st
 from .ec import ReedSolomon
 
 
+def _rebuild_interleaved(rs, slice_type, fragments, erased, want, device):
+    """rebuild_part_images for INTERLEAVED images: recover straight into
+    the images' blocks (strided EC kernel), then fill the CRC slots."""
+    doff, coff, bstride, cstride = scrub.image_layout("interleaved",
+                                                      slice_type)
+    surv = [f for i, f in enumerate(fragments)
+            if f is not None and i not in set(erased)]
+    if not surv:
+        raise ValueError("all surviving parts are None")
+    S, plen = surv[0].shape
+    if plen % st.BLOCK_SIZE:
+        raise ValueError("part length must be whole 64 KiB blocks")
+    nblocks = plen // st.BLOCK_SIZE
+    parts = sorted(set(want) if want is not None else set(erased))
+    imgs = {p: torch.empty((S, nblocks * bstride), dtype=torch.uint8,
+                           device=surv[0].device) for p in parts}
+    rs.recover_batch_blocks(fragments, erased, want=parts,
+                            out={p: imgs[p][:, doff:] for p in parts},
+                            nblocks=nblocks, dst_stride=bstride)
+    n = S * len(parts)
+    dptrs = np.array([imgs[p].data_ptr() + s * nblocks * bstride
+                      for p in parts for s in range(S)], np.uint64)
+    doffs = np.full(n, doff, np.uint32)
+    coffs = np.full(n, coff, np.uint32)
+    counts = np.full(n, nblocks, np.uint32)
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    L.check(L.lib().lizec_crc_fill_batch_strided(
+        L.engine(device), dptrs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+        doffs.ctypes.data_as(u32p), coffs.ctypes.data_as(u32p),
+        counts.ctypes.data_as(u32p), n, bstride, cstride,
+        ctypes.c_void_p(stream)), "lizec_crc_fill_batch_strided")
+    return {(s, p): imgs[p][s] for p in parts for s in range(S)}
+
+
 def rebuild_part_images(k, m, fragments, erased, want, chunk_ids, version,
-                        device=0):
-    """Recover the `want` parts of a batch of chunks and build their
-    MooseFS part images on the GPU.
+                        device=0, fmt="moosefs"):
+    """Recover the `want` parts of a batch of chunks and build their part
+    images on the GPU, in either on-disk format.
 
     fragments: list of k+m entries ([S, L] uint8 CUDA tensors or None),
       part data only (no headers), L a multiple of 64 KiB; row s belongs
       to chunk chunk_ids[s].
     erased: exactly m part indices (pad like ec_read_plan.h:126-133).
     want: subset of erased to rebuild.
+    fmt: "moosefs" (default) or "interleaved" (no header or signature, each
+      block preceded by its CRC; chunk_ids and version are unused there).
     Returns dict (chunk_index s, part_index) -> image tensor; image layout
     per chunkserver/chunk.cc (scrub.py geometry), CRC array filled by the
     GPU crc32_blocks kernel, signature per chunk_signature.cc:87-90.
     """
-    rs = ReedSolomon(k, m, device=device)
     slice_type = st.ec_slice_type(k, m)
+    scrub.image_layout(fmt, slice_type)     # refuses an unknown fmt
+    rs = ReedSolomon(k, m, device=device)
+    if fmt == "interleaved":
+        return _rebuild_interleaved(rs, slice_type, fragments, erased, want,
+                                    device)
     rec = rs.recover_batch(fragments, erased=erased, want=want)
 
     out = {}
@@ -64,7 +105,7 @@ def rebuild_part_images(k, m, fragments, erased, want, chunk_ids, version,
 
 
 def replicate_stream(k, m, host_parts, erased, want, chunk_ids, version,
-                     out=None, device=0, sub_batch=0):
+                     out=None, device=0, sub_batch=0, fmt="moosefs"):
     """The full ChunkReplicator::replicate pipeline
     (chunk_replicator.cc:139-196), host-to-host and streaming: surviving
     parts in HOST memory -> H2D -> recover -> per-block CRC -> MooseFS part
@@ -76,9 +117,16 @@ def replicate_stream(k, m, host_parts, erased, want, chunk_ids, version,
     erased: exactly m part indices; want: subset to rebuild.
     out: optional dict part -> uint8 [S, hdr+L] array to fill (pinned
       recommended); allocated (pinned) if absent.
+    fmt: "moosefs" (default) or "interleaved"
+      (lizec_replicate_run_interleaved): images of (L/65536)*65540 bytes,
+      no header or signature, each block preceded by its big-endian CRC;
+      chunk_ids and version are unused there.
     Returns dict part -> [S, hdr+L] images (signature + BE CRC array +
     recovered blocks), pwrite-ready.
     """
+    if fmt not in scrub.FORMATS:
+        raise ValueError(f"unknown chunk format {fmt!r} "
+                         f"(one of {scrub.FORMATS})")
     nparts = k + m
     if len(host_parts) != nparts:
         raise ValueError(f"need {nparts} part slots")
@@ -121,11 +169,14 @@ def replicate_stream(k, m, host_parts, erased, want, chunk_ids, version,
     ic, oc = ic.value, oc.value
     assert (ic, oc) == (len(surv), len(want))
 
+    img_bytes = hdr + plen
+    if fmt == "interleaved":
+        img_bytes = plen // st.BLOCK_SIZE * scrub.HDD_BLOCK
     if out is None:
-        out = {p: L.pinned_empty((S, hdr + plen)) for p in want}
+        out = {p: L.pinned_empty((S, img_bytes)) for p in want}
     for p in want:
-        if out[p].dtype != np.uint8 or out[p].shape != (S, hdr + plen):
-            raise ValueError(f"out[{p}] must be uint8 [S={S}, {hdr + plen}]")
+        if out[p].dtype != np.uint8 or out[p].shape != (S, img_bytes):
+            raise ValueError(f"out[{p}] must be uint8 [S={S}, {img_bytes}]")
 
     src = np.empty((S, ic), np.uint64)
     for j, i in enumerate(surv):
@@ -138,11 +189,21 @@ def replicate_stream(k, m, host_parts, erased, want, chunk_ids, version,
         a = out[p]
         dst[:, j] = a.ctypes.data + np.arange(S, dtype=np.uint64) * \
             np.uint64(a.strides[0])
-        for s in range(S):
+        for s in range(S if fmt == "moosefs" else 0):
             sig = scrub.build_signature(int(chunk_ids[s]), version,
                                         slice_type, p)
             sigs[s, j, :len(sig)] = np.frombuffer(sig, np.uint8)
 
+    if fmt == "interleaved":
+        L.check(lib.lizec_replicate_run_interleaved(
+            L.engine(device), plen, ic, oc,
+            tbl.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+            np.ascontiguousarray(src.ravel()).ctypes.data_as(
+                ctypes.POINTER(ctypes.c_uint64)),
+            np.ascontiguousarray(dst.ravel()).ctypes.data_as(
+                ctypes.POINTER(ctypes.c_uint64)),
+            S, sub_batch), "lizec_replicate_run_interleaved")
+        return out
     L.check(lib.lizec_replicate_run(
         L.engine(device), plen, ic, oc,
         tbl.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),

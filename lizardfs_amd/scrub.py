@@ -41,6 +41,23 @@ def header_size(slice_type):
     return (req + DISK_BLOCK - 1) // DISK_BLOCK * DISK_BLOCK
 
 
+FORMATS = ("moosefs", "interleaved")
+
+
+def image_layout(fmt, slice_type):
+    """Where a part-file image of either on-disk format keeps its blocks
+    and CRCs: (data_off, crc_off, block_stride, crc_stride) — block b's
+    data at data_off + b*block_stride, its big-endian CRC at
+    crc_off + b*crc_stride.  MooseFS (chunk.cc:126-188): CRC array at 1024,
+    blocks after the header.  INTERLEAVED (chunk.cc:191-209): no header,
+    each block preceded by its own CRC."""
+    if fmt == "moosefs":
+        return header_size(slice_type), SIGNATURE_BLOCK, st.BLOCK_SIZE, 4
+    if fmt == "interleaved":
+        return 4, 0, HDD_BLOCK, HDD_BLOCK
+    raise ValueError(f"unknown chunk format {fmt!r} (one of {FORMATS})")
+
+
 def build_signature(chunk_id, version, slice_type, part):
     """chunk_signature.cc:87-90 (LIZC 1.1 serialization, big-endian)."""
     pid = st.chunk_part_id(slice_type, part)
