@@ -257,6 +257,60 @@ int lizec_ec_encode_batch_strided(lizec_engine *e, uint32_t nblocks, int srcs,
                                   uint32_t src_block_stride,
                                   uint32_t dst_block_stride, void *stream);
 
+/* Batched EC encode/decode over parts of DIFFERENT lengths: the strided
+ * call above with a block count per source and per destination of every
+ * stripe, and a coefficient table per stripe.  A chunk is 1..1024 blocks
+ * and only a full one gives its parts a common length — data part p of a
+ * chunk of n blocks has (n + k - p - 1) / k blocks (slice_traits.h:311-316)
+ * — so one call rebuilds chunks of any mix of lengths and erasure patterns,
+ * straight into images of either on-disk format
+ * (ChunkReplicator::replicate, chunk_replicator.cc:142-145).
+ *  gftbls, ntables, tbl_index: as for lizec_ec_encode_batch_multi;
+ *             tbl_index may be NULL = every stripe uses table 0
+ *  src_dptrs / src_nblocks: HOST arrays [num_stripes][srcs]: address of
+ *             block 0's data and number of blocks of every source.  Source
+ *             j takes part in block b iff b < its count; beyond that it
+ *             counts as zeros and no byte of it is read — the reference's
+ *             NULL-part rule (reed_solomon.h:79) per block.  An address
+ *             whose count is 0 is never used and may be 0.
+ *  dst_dptrs / dst_nblocks: HOST arrays [num_stripes][dests], likewise:
+ *             destination l is written for block b iff b < its count; a
+ *             block that no source covers is written as zeros.  A stripe
+ *             whose destination counts are all 0 is legal and costs nothing.
+ *  src_block_stride / dst_block_stride: as for the strided call
+ * Only bytes inside the counted blocks are read or written.
+ * Returns LIZEC_EINVAL from the host, with nothing enqueued, if a stride or
+ * a used address is not a multiple of 4, a stride is below 65536, srcs or
+ * dests is outside 1..32, a count exceeds 32768, a nonzero count comes with
+ * address 0, a tbl_index entry is >= ntables, ntables is outside the limits
+ * of the multi call, no destination has any block, or the block rows of the
+ * batch (lizec_ragged_block_map) times 8 exceed 2^31-1.
+ * A side whose stride and used addresses are all multiples of 16 keeps the
+ * aligned vector accesses.  There is no plan form.  Stream and thread
+ * contract as for the other batch calls. */
+int lizec_ec_encode_batch_ragged(lizec_engine *e, int srcs, int dests,
+                                 const uint8_t *gftbls, int ntables,
+                                 const uint32_t *tbl_index,
+                                 const uint64_t *src_dptrs,
+                                 const uint32_t *src_nblocks,
+                                 const uint64_t *dst_dptrs,
+                                 const uint32_t *dst_nblocks, int num_stripes,
+                                 uint32_t src_block_stride,
+                                 uint32_t dst_block_stride, void *stream);
+
+/* The block map of a ragged batch; pure host code, needs no GPU.  One
+ * entry (stripe, block) per 64 KiB block row: stripe s contributes blocks
+ * 0 .. max_l dst_nblocks[s][l] - 1, stripe-major, ascending.
+ *  map        : 2 words per entry, or NULL to count only
+ *  cap_entries: room in map, in entries
+ * Returns the entry count (0 if no destination has a block), or
+ * LIZEC_EINVAL if dests is outside 1..32, num_stripes < 1, a count exceeds
+ * 32768, the entries do not fit cap_entries, or entries*8 > 2^31-1 (the
+ * batch counted in 8 KiB tiles, one workgroup each). */
+int64_t lizec_ragged_block_map(const uint32_t *dst_nblocks, int dests,
+                               int num_stripes, uint32_t *map,
+                               uint64_t cap_entries);
+
 /* Per-block CRC32 over a contiguous device buffer:
  *  dev_crcs_out[b] = lizec_crc32(seed, dev_buf + b*block_len, block_len)
  * The chunkserver's per-64KiB-block gate (hddspacemgr.cc:1918-1920, scrub

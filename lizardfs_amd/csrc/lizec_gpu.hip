@@ -41,6 +41,7 @@
 #include "ec_kernel.h"
 #include "ec_kernel_multi.h"
 #include "ec_kernel_strided.h"
+#include "ec_kernel_ragged.h"
 #include "crc_fold.h"
 
 /* Product kernel configuration (chosen by the variant A/B harness,
@@ -385,6 +386,13 @@ struct lizec_stream_ctx {
 	size_t mindex_cap = 0;          /* in elements */
 	uint8_t *h_mstaging = nullptr;  /* pinned: packed tables + index */
 	size_t h_mcap = 0;              /* bytes */
+	/* ragged batches only (lizec_ec_encode_batch_ragged): one device buffer
+	 * holding packed tables, table index, block map and the two block-count
+	 * arrays, and its pinned mirror; guarded by the same `uploaded` event.
+	 * Never allocated for callers of the other entry points. */
+	uint8_t *d_ragged = nullptr;    /* grows */
+	uint8_t *h_ragged = nullptr;    /* pinned, same size */
+	size_t ragged_cap = 0;          /* bytes */
 };
 
 struct lizec_engine {
@@ -406,6 +414,8 @@ static void ctx_free(lizec_stream_ctx &c) {
 	(void)hipFree(c.d_mtbls);
 	(void)hipFree(c.d_mindex);
 	(void)hipHostFree(c.h_mstaging);
+	(void)hipFree(c.d_ragged);
+	(void)hipHostFree(c.h_ragged);
 	if (c.uploaded) (void)hipEventDestroy(c.uploaded);
 	c = lizec_stream_ctx();
 }
@@ -496,6 +506,28 @@ static int ctx_acquire_multi(lizec_engine *e, hipStream_t s, size_t ptrs,
 		c.h_mcap = 0;
 		LIZEC_CHECK(hipHostMalloc(&c.h_mstaging, cap));
 		c.h_mcap = cap;
+	}
+	return LIZEC_OK;
+}
+
+/* ctx_acquire plus the ragged scratch: `bytes` on the device and as many
+ * pinned.  As in ctx_acquire_multi the previous call's uploads are over. */
+static int ctx_acquire_ragged(lizec_engine *e, hipStream_t s, size_t ptrs,
+                              size_t staging, size_t bytes,
+                              lizec_stream_ctx **out) {
+	int r = ctx_acquire(e, s, ptrs, staging, out);
+	if (r != LIZEC_OK) return r;
+	lizec_stream_ctx &c = **out;
+	if (c.ragged_cap < bytes) {
+		size_t cap = c.ragged_cap ? c.ragged_cap : (1 << 17);
+		while (cap < bytes) cap *= 2;
+		(void)hipFree(c.d_ragged);
+		(void)hipHostFree(c.h_ragged);
+		c.d_ragged = c.h_ragged = nullptr;
+		c.ragged_cap = 0;
+		LIZEC_CHECK(hipMalloc(&c.d_ragged, cap));
+		LIZEC_CHECK(hipHostMalloc(&c.h_ragged, cap));
+		c.ragged_cap = cap;
 	}
 	return LIZEC_OK;
 }
@@ -848,6 +880,151 @@ extern "C" int lizec_ec_encode_batch_strided(
 	return run_batch_strided(nblocks, srcs, dests, c->d_gftbls, d_src, d_dst,
 	                         (uint32_t)num_stripes, src_block_stride,
 	                         dst_block_stride, sal, dal, s);
+}
+
+/* ------------------------------------------------------------------ */
+/* Ragged batches: a block count per part (ec_kernel_ragged.h)        */
+/* ------------------------------------------------------------------ */
+
+struct ragged_dev {
+	const uint8_t *tbls;
+	const uint32_t *index;
+	const uint2 *map;
+	const uint64_t *src, *dst;
+	const uint32_t *src_nb, *dst_nb;
+};
+
+/* One pass of the ragged kernel: one workgroup per tile of every block row
+ * in the map. */
+template <int D>
+static void launch_ec_ragged(uint32_t entries, int srcs, int dest_base,
+                             const ragged_dev &r, int dests_total,
+                             uint32_t src_stride, uint32_t dst_stride,
+                             bool sal, bool dal, hipStream_t s) {
+	constexpr int CH = ec_chunks_for(D);
+	uint32_t total_tiles = entries * (kECBlockBytes / (kChunkBytes * CH));
+	size_t lds = (size_t)D * srcs * kECTblBytes;
+#define LIZEC_LAUNCH_RAGGED(SAL, DAL)                                       \
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(ec_encode_ragged_kernel<D, CH, SAL, DAL>), \
+	                   dim3(total_tiles), dim3(kThreads), lds, s, srcs,     \
+	                   dest_base, r.tbls, r.index, r.map, r.src, r.src_nb,  \
+	                   r.dst, r.dst_nb, dests_total, src_stride, dst_stride)
+	if (sal && dal) LIZEC_LAUNCH_RAGGED(true, true);
+	else if (sal) LIZEC_LAUNCH_RAGGED(true, false);
+	else if (dal) LIZEC_LAUNCH_RAGGED(false, true);
+	else LIZEC_LAUNCH_RAGGED(false, false);
+#undef LIZEC_LAUNCH_RAGGED
+}
+
+extern "C" int lizec_ec_encode_batch_ragged(
+    lizec_engine *e, int srcs, int dests, const uint8_t *gftbls, int ntables,
+    const uint32_t *tbl_index, const uint64_t *src_dptrs,
+    const uint32_t *src_nblocks, const uint64_t *dst_dptrs,
+    const uint32_t *dst_nblocks, int num_stripes, uint32_t src_block_stride,
+    uint32_t dst_block_stride, void *stream) {
+	if (!e || !gftbls || !src_dptrs || !src_nblocks || !dst_dptrs ||
+	    !dst_nblocks)
+		return LIZEC_EINVAL;
+	if (srcs < 1 || srcs > 32 || dests < 1 || dests > 32 || num_stripes < 1)
+		return LIZEC_EINVAL;
+	if (ntables < 1 ||
+	    (uint64_t)ntables * 32 * srcs * dests > (uint64_t)1 << 30)
+		return LIZEC_EINVAL;
+	if (src_block_stride < kECBlockBytes || dst_block_stride < kECBlockBytes)
+		return LIZEC_EINVAL;
+	if (tbl_index)
+		for (int i = 0; i < num_stripes; ++i)
+			if (tbl_index[i] >= (uint32_t)ntables) return LIZEC_EINVAL;
+	size_t nsrc = (size_t)num_stripes * srcs;
+	size_t ndst = (size_t)num_stripes * dests;
+	/* per side, the OR of the stride and of the addresses that are used
+	 * (count > 0) decides between refusal, the dword-aligned kernel forms
+	 * and the 16-byte-aligned ones; an unused address may be anything */
+	uint64_t sbits = src_block_stride, dbits = dst_block_stride;
+	for (size_t i = 0; i < nsrc; ++i) {
+		if (src_nblocks[i] > 32768u) return LIZEC_EINVAL;
+		if (!src_nblocks[i]) continue;
+		if (!src_dptrs[i]) return LIZEC_EINVAL;
+		sbits |= src_dptrs[i];
+	}
+	for (size_t i = 0; i < ndst; ++i) {
+		if (dst_nblocks[i] > 32768u) return LIZEC_EINVAL;
+		if (!dst_nblocks[i]) continue;
+		if (!dst_dptrs[i]) return LIZEC_EINVAL;
+		dbits |= dst_dptrs[i];
+	}
+	if ((sbits | dbits) & 3) return LIZEC_EINVAL;
+	const bool sal = (sbits & 15) == 0, dal = (dbits & 15) == 0;
+	/* counts the block rows and refuses a batch of more than 2^31-1 tiles */
+	int64_t entries =
+	    lizec_ragged_block_map(dst_nblocks, dests, num_stripes, nullptr, 0);
+	if (entries <= 0) return LIZEC_EINVAL;
+	hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+	LIZEC_CHECK(hipSetDevice(e->device));
+
+	/* scratch layout, every section 16-byte aligned */
+	auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+	size_t ntbl = (size_t)ntables * srcs * dests;   /* 32-byte tables */
+	size_t o_index = up16(ntbl * kECTblBytes);
+	size_t o_map = o_index + up16((size_t)num_stripes * 4);
+	size_t o_snb = o_map + up16((size_t)entries * 8);
+	size_t o_dnb = o_snb + up16(nsrc * 4);
+	size_t bytes = o_dnb + up16(ndst * 4);
+	lizec_stream_ctx *c;
+	int r = ctx_acquire_ragged(e, s, nsrc + ndst, (nsrc + ndst) * 8, bytes, &c);
+	if (r != LIZEC_OK) return r;
+	uint8_t *h = c->h_ragged;
+	for (size_t i = 0; i < ntbl; ++i)
+		pack_mixed_radix(gftbls + i * 32, h + i * kECTblBytes);
+	if (tbl_index)
+		memcpy(h + o_index, tbl_index, (size_t)num_stripes * 4);
+	else
+		memset(h + o_index, 0, (size_t)num_stripes * 4);
+	if (lizec_ragged_block_map(dst_nblocks, dests, num_stripes,
+	                           (uint32_t *)(h + o_map),
+	                           (uint64_t)entries) != entries)
+		return LIZEC_EINVAL;
+	memcpy(h + o_snb, src_nblocks, nsrc * 4);
+	memcpy(h + o_dnb, dst_nblocks, ndst * 4);
+	uint64_t *pstage = (uint64_t *)(c->h_staging + (size_t)kECTblBytes * 32 * 32);
+	memcpy(pstage, src_dptrs, nsrc * 8);
+	memcpy(pstage + nsrc, dst_dptrs, ndst * 8);
+	LIZEC_CHECK(hipMemcpyAsync(c->d_ragged, h, bytes, hipMemcpyHostToDevice, s));
+	LIZEC_CHECK(hipMemcpyAsync(c->d_ptrs, pstage, (nsrc + ndst) * 8,
+	                           hipMemcpyHostToDevice, s));
+	LIZEC_CHECK(hipEventRecord(c->uploaded, s));
+	c->ev_recorded = true;
+
+	ragged_dev rd;
+	rd.tbls = c->d_ragged;
+	rd.index = (const uint32_t *)(c->d_ragged + o_index);
+	rd.map = (const uint2 *)(c->d_ragged + o_map);
+	rd.src_nb = (const uint32_t *)(c->d_ragged + o_snb);
+	rd.dst_nb = (const uint32_t *)(c->d_ragged + o_dnb);
+	rd.src = c->d_ptrs;
+	rd.dst = c->d_ptrs + nsrc;
+	/* passes of at most 8 destinations, as run_batch_strided */
+	for (int base = 0; base < dests;) {
+		int d = dests - base;
+		if (d > 8) d = 8;
+#define LIZEC_LAUNCH_RAGGED_D(D)                                           \
+	launch_ec_ragged<D>((uint32_t)entries, srcs, base, rd, dests,          \
+	                    src_block_stride, dst_block_stride, sal, dal, s)
+		switch (d) {
+		case 1: LIZEC_LAUNCH_RAGGED_D(1); break;
+		case 2: LIZEC_LAUNCH_RAGGED_D(2); break;
+		case 3: LIZEC_LAUNCH_RAGGED_D(3); break;
+		case 4: LIZEC_LAUNCH_RAGGED_D(4); break;
+		case 5: LIZEC_LAUNCH_RAGGED_D(5); break;
+		case 6: LIZEC_LAUNCH_RAGGED_D(6); break;
+		case 7: LIZEC_LAUNCH_RAGGED_D(7); break;
+		default: LIZEC_LAUNCH_RAGGED_D(8); break;
+		}
+#undef LIZEC_LAUNCH_RAGGED_D
+		base += d;
+	}
+	LIZEC_CHECK(hipGetLastError());
+	return LIZEC_OK;
 }
 
 /* Multi-table launch: same grid/tile/LDS shape as launch_ec. */

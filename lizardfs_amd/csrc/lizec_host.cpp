@@ -488,3 +488,40 @@ extern "C" int64_t lizec_chunk_part_length(int slice_type, int part,
 	if (part_rest > kBlockSize) part_rest = kBlockSize;
 	return base_len + part_rest;
 }
+
+/* ------------------------------------------------------------------ */
+/* Ragged EC batches: the block map (pure host, no GPU)               */
+/* ------------------------------------------------------------------ */
+
+extern "C" int64_t lizec_ragged_block_map(const uint32_t *dst_nblocks,
+                                          int dests, int num_stripes,
+                                          uint32_t *map,
+                                          uint64_t cap_entries) {
+	if (!dst_nblocks || dests < 1 || dests > 32 || num_stripes < 1)
+		return LIZEC_EINVAL;
+	uint64_t entries = 0;
+	for (int s = 0; s < num_stripes; ++s) {
+		uint32_t nb = 0;
+		for (int l = 0; l < dests; ++l) {
+			uint32_t n = dst_nblocks[(size_t)s * dests + l];
+			if (n > 32768u) return LIZEC_EINVAL;
+			if (n > nb) nb = n;
+		}
+		entries += nb;
+	}
+	/* one workgroup per 8 KiB tile at the most, in a 31-bit grid */
+	if (entries * 8 > 0x7FFFFFFFull) return LIZEC_EINVAL;
+	if (!map) return (int64_t)entries;
+	if (entries > cap_entries) return LIZEC_EINVAL;
+	for (int s = 0; s < num_stripes; ++s) {
+		uint32_t nb = 0;
+		for (int l = 0; l < dests; ++l)
+			if (dst_nblocks[(size_t)s * dests + l] > nb)
+				nb = dst_nblocks[(size_t)s * dests + l];
+		for (uint32_t b = 0; b < nb; ++b) {
+			*map++ = (uint32_t)s;
+			*map++ = b;
+		}
+	}
+	return (int64_t)entries;
+}

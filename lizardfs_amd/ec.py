@@ -568,5 +568,173 @@ class ReedSolomon:
                 "lizec_ec_plan_run")
         return outs, slots
 
+    def _per_stripe_sets(self, sets, S, what):
+        """One index set for all stripes, or one per stripe -> per stripe."""
+        if isinstance(sets, np.ndarray):
+            if sets.ndim == 2:
+                per = sets
+            elif sets.ndim == 1:
+                per = np.broadcast_to(sets, (S, sets.shape[0]))
+                per = np.ascontiguousarray(per)
+            else:
+                raise ValueError(f"{what}: expected 1 or 2 dimensions")
+        else:
+            sets = list(sets)
+            if sets and all(isinstance(i, (int, np.integer)) for i in sets):
+                per = [sets] * S
+            else:
+                per = sets
+        if len(per) != S:
+            raise ValueError(f"{what} has {len(per)} entries for {S} stripes")
+        return per
+
+    def _ragged_prepare(self, fragments, erased, want, part_blocks,
+                        src_stride, allow_empty=False):
+        """Argument checks and the source side of a ragged call:
+        (S, device, tables, index, slots, src addresses [S, k], src counts
+        [S, k], dst counts [S, oc])."""
+        nparts = self.k + self.m
+        if len(fragments) != nparts:
+            raise ValueError(f"need {nparts} fragment slots")
+        pb = np.asarray(part_blocks)
+        if pb.ndim != 2 or pb.shape[1] != nparts or pb.shape[0] < 1 or \
+                pb.dtype.kind not in "iu":
+            raise ValueError(f"part_blocks must be an int array "
+                             f"[S, {nparts}]")
+        if pb.min() < 0 or pb.max() > 32768:
+            raise ValueError("part_blocks out of [0, 32768]")
+        pb = pb.astype(np.int64)
+        S = pb.shape[0]
+        if src_stride < _BLOCK or src_stride % 4:
+            raise ValueError(f"src_stride={src_stride} must be a multiple "
+                             f"of 4 and at least {_BLOCK}")
+        erased = self._per_stripe_sets(erased, S, "erased")
+        if want is not None:
+            want = self._per_stripe_sets(want, S, "want")
+        tables, index, pslots, pemask = _pattern_tables(self.k, self.m,
+                                                        erased, want)
+        slots = pslots[index]
+        # sources: each pattern's k surviving parts in ascending order
+        palive = np.array(
+            [[i for i in range(nparts) if not (int(e) >> i) & 1]
+             for e in pemask], np.intp)
+        alive = palive[index]                                  # [S, k]
+        read = np.zeros(nparts, bool)
+        read[np.unique(alive)] = True
+        bases = np.zeros(nparts, np.uint64)
+        strides = np.zeros(nparts, np.uint64)
+        dev = None
+        for i, t in enumerate(fragments):
+            if t is None:
+                if read[i]:
+                    raise ValueError(f"fragment {i} is None but survives in "
+                                     f"some stripe")
+                continue
+            s, span, rstride = self._frag_geom(t, f"fragment {i}")
+            if s != S:
+                raise ValueError(f"fragment {i} has {s} rows, expected {S}")
+            top = int(pb[:, i].max())
+            need = (top - 1) * src_stride + _BLOCK if top else 0
+            if span < need:
+                raise ValueError(f"fragment {i}: rows of {span} bytes cannot "
+                                 f"hold {top} blocks at stride {src_stride} "
+                                 f"({need} bytes)")
+            if t.data_ptr() % 4 or (s > 1 and rstride % 4):
+                raise ValueError(f"fragment {i}: block data must be 4-byte "
+                                 f"aligned (address {t.data_ptr():#x}, row "
+                                 f"stride {rstride})")
+            dev = t.device
+            bases[i] = t.data_ptr()
+            strides[i] = rstride
+        if dev is None:
+            raise ValueError("all fragments are None")
+        rows = np.arange(S, dtype=np.uint64)[:, None]
+        src = np.ascontiguousarray(bases[alive] + rows * strides[alive])
+        src_nb = np.ascontiguousarray(
+            np.take_along_axis(pb, alive, axis=1).astype(np.uint32))
+        dst_nb = np.take_along_axis(pb, np.maximum(slots, 0), axis=1)
+        dst_nb = np.ascontiguousarray(
+            np.where(slots >= 0, dst_nb, 0).astype(np.uint32))
+        if not allow_empty and not dst_nb.any():
+            raise ValueError("no wanted part has any block")
+        return S, dev, tables, index, slots, src, src_nb, dst_nb
+
+    def _ragged_call(self, tables, index, src, src_nb, dst, dst_nb,
+                     src_stride, dst_stride):
+        """lizec_ec_encode_batch_ragged over prepared host arrays."""
+        S, oc = dst_nb.shape
+        u8p = ctypes.POINTER(ctypes.c_uint8)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        dst = np.ascontiguousarray(dst, np.uint64)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        L.check(self._lib.lizec_ec_encode_batch_ragged(
+            self._engine, self.k, oc, tables.ctypes.data_as(u8p),
+            tables.shape[0], index.ctypes.data_as(u32p),
+            src.ctypes.data_as(u64p), src_nb.ctypes.data_as(u32p),
+            dst.ctypes.data_as(u64p), dst_nb.ctypes.data_as(u32p), S,
+            src_stride, dst_stride, ctypes.c_void_p(stream)),
+            "lizec_ec_encode_batch_ragged")
+
+    def recover_batch_ragged(self, fragments, erased, want=None, out=None, *,
+                             part_blocks, src_stride=_BLOCK,
+                             dst_stride=_BLOCK):
+        """Recover missing parts for a batch whose chunks differ in length
+        (and, if wanted, in erasure pattern) in one call
+        (lizec_ec_encode_batch_ragged): the ragged sibling of
+        recover_batch_mixed and recover_batch_blocks.
+
+        part_blocks: int array [S, k+m], 64 KiB blocks of every part of
+          every stripe (slice_traits.number_of_blocks of the chunk's block
+          count); a part ends where the zeros past the end of its chunk
+          begin.
+        erased / want: one index set for all stripes, or per-stripe sets as
+          in build_pattern_tables.
+        fragments: list of k+m [S, span] row views as in
+          recover_batch_blocks; span must cover the largest count of that
+          part.  Blocks at or beyond part_blocks[s, i] are never read and
+          count as zeros.  None is allowed only for a part that is erased
+          in every stripe.
+        out: optional [S, oc, span_out] uint8 CUDA tensor with contiguous
+          rows (a view is fine), blocks at dst_stride; required unless
+          dst_stride is 65536.
+        Returns (out [S, oc, span_out], slots [S, oc]) as
+        recover_batch_mixed does; of out[s, j] only the blocks below
+        part_blocks[s, slots[s, j]] are written.  Encode is the case
+        erased = want = the parity parts.
+        """
+        if dst_stride < _BLOCK or dst_stride % 4:
+            raise ValueError(f"dst_stride={dst_stride} must be a multiple "
+                             f"of 4 and at least {_BLOCK}")
+        if out is None and dst_stride != _BLOCK:
+            raise ValueError("out is required when dst_stride != 65536")
+        S, dev, tables, index, slots, src, src_nb, dst_nb = \
+            self._ragged_prepare(fragments, erased, want, part_blocks,
+                                 src_stride)
+        oc = slots.shape[1]
+        need = (int(dst_nb.max()) - 1) * dst_stride + _BLOCK
+        if out is None:
+            out = torch.empty((S, oc, need), dtype=torch.uint8, device=dev)
+        else:
+            if out.dtype != torch.uint8 or not out.is_cuda or \
+                    out.dim() != 3 or out.stride(2) != 1 or \
+                    tuple(out.shape[:2]) != (S, oc):
+                raise ValueError(f"out must be a CUDA uint8 [S={S}, oc={oc}, "
+                                 f"span] tensor with contiguous rows")
+            if out.shape[2] < need:
+                raise ValueError(f"out: rows of {out.shape[2]} bytes cannot "
+                                 f"hold {int(dst_nb.max())} blocks at stride "
+                                 f"{dst_stride} ({need} bytes)")
+            if out.data_ptr() % 4 or out.stride(0) % 4 or out.stride(1) % 4:
+                raise ValueError("out: block data must be 4-byte aligned")
+        dst = (np.uint64(out.data_ptr()) +
+               np.arange(S, dtype=np.uint64)[:, None] *
+               np.uint64(out.stride(0)) +
+               np.arange(oc, dtype=np.uint64)[None, :] *
+               np.uint64(out.stride(1)))
+        self._ragged_call(tables, index, src, src_nb, dst, dst_nb,
+                          src_stride, dst_stride)
+        return out, slots
+
     def sync(self):
         L.check(self._lib.lizec_engine_sync(self._engine))

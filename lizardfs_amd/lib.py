@@ -124,6 +124,16 @@ def lib():
         ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, u8p,
         ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
         ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    L.lizec_ec_encode_batch_ragged.restype = ctypes.c_int
+    L.lizec_ec_encode_batch_ragged.argtypes = [
+        ctypes.c_void_p, ctypes.c_int, ctypes.c_int, u8p, ctypes.c_int, u32p,
+        u64p, u32p, u64p, u32p, ctypes.c_int, ctypes.c_uint32,
+        ctypes.c_uint32, ctypes.c_void_p]
+    L.lizec_ragged_block_map.restype = ctypes.c_int64
+    L.lizec_ragged_block_map.argtypes = [
+        u32p, ctypes.c_int, ctypes.c_int, u32p, ctypes.c_uint64]
     L.lizec_crc_fill_batch_strided.restype = ctypes.c_int
     L.lizec_crc_fill_batch_strided.argtypes = [
         ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),

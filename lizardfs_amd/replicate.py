@@ -55,8 +55,75 @@ def _rebuild_interleaved(rs, slice_type, fragments, erased, want, device):
     return {(s, p): imgs[p][s] for p in parts for s in range(S)}
 
 
+def _rebuild_ragged(rs, slice_type, fragments, erased, want, chunk_ids,
+                    version, device, fmt, chunk_blocks):
+    """rebuild_part_images for chunks of different lengths: every image has
+    its own size; all of them are recovered in place by one ragged EC call
+    and their CRCs filled by one call with per-image block counts."""
+    doff, coff, bstride, cstride = scrub.image_layout(fmt, slice_type)
+    nparts = rs.k + rs.m
+    cb = np.asarray(chunk_blocks)
+    if cb.ndim != 1 or cb.size < 1 or cb.dtype.kind not in "iu":
+        raise ValueError("chunk_blocks must be a 1-D int sequence")
+    if cb.min() < 1 or cb.max() > st.BLOCKS_IN_CHUNK:
+        raise ValueError(f"chunk_blocks out of [1, {st.BLOCKS_IN_CHUNK}]")
+    S = cb.size
+    if fmt == "moosefs" and len(chunk_ids) != S:
+        raise ValueError("need one chunk id per chunk")
+    part_blocks = np.array(
+        [[st.number_of_blocks(slice_type, i, int(n)) for i in range(nparts)]
+         for n in cb], np.int64)
+    S, dev, tables, index, slots, src, src_nb, dst_nb = rs._ragged_prepare(
+        fragments, erased, want, part_blocks, st.BLOCK_SIZE,
+        allow_empty=True)
+    oc = slots.shape[1]
+    # one arena; image (s, j) at offs[s, j], sized for its own block count
+    used = slots >= 0
+    head = doff if fmt == "moosefs" else 0
+    sizes = np.where(used, head + dst_nb.astype(np.int64) *
+                     (st.BLOCK_SIZE if fmt == "moosefs" else bstride), 0)
+    offs = np.concatenate([[0], np.cumsum(sizes.ravel())[:-1]]).reshape(S, oc)
+    arena = torch.empty(max(int(sizes.sum()), 1), dtype=torch.uint8,
+                        device=dev)
+    images = {}
+    pairs = [(s, j) for s in range(S) for j in range(oc) if used[s, j]]
+    for s, j in pairs:
+        images[(s, int(slots[s, j]))] = \
+            arena[int(offs[s, j]):int(offs[s, j] + sizes[s, j])]
+    if fmt == "moosefs":
+        # headers: zeros but for the signature; the CRC array is filled below
+        hdrs = np.zeros((len(pairs), doff), np.uint8)
+        for n, (s, j) in enumerate(pairs):
+            sig = scrub.build_signature(int(chunk_ids[s]), version,
+                                        slice_type, int(slots[s, j]))
+            hdrs[n, :len(sig)] = np.frombuffer(sig, np.uint8)
+        hdrs = torch.from_numpy(hdrs).to(dev)
+        for n, (s, j) in enumerate(pairs):
+            images[(s, int(slots[s, j]))][:doff] = hdrs[n]
+    base = np.uint64(arena.data_ptr()) + offs.astype(np.uint64)
+    fill = [(s, j) for s, j in pairs if dst_nb[s, j]]
+    if fill:
+        rs._ragged_call(tables, index, src, src_nb,
+                        np.where(used, base + np.uint64(doff), np.uint64(0)),
+                        dst_nb, st.BLOCK_SIZE, bstride)
+        n = len(fill)
+        dptrs = np.array([base[s, j] for s, j in fill], np.uint64)
+        doffs = np.full(n, doff, np.uint32)
+        coffs = np.full(n, coff, np.uint32)
+        counts = np.array([dst_nb[s, j] for s, j in fill], np.uint32)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        L.check(L.lib().lizec_crc_fill_batch_strided(
+            L.engine(device),
+            dptrs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+            doffs.ctypes.data_as(u32p), coffs.ctypes.data_as(u32p),
+            counts.ctypes.data_as(u32p), n, bstride, cstride,
+            ctypes.c_void_p(stream)), "lizec_crc_fill_batch_strided")
+    return images
+
+
 def rebuild_part_images(k, m, fragments, erased, want, chunk_ids, version,
-                        device=0, fmt="moosefs"):
+                        device=0, fmt="moosefs", chunk_blocks=None):
     """Recover the `want` parts of a batch of chunks and build their part
     images on the GPU, in either on-disk format.
 
@@ -67,6 +134,14 @@ def rebuild_part_images(k, m, fragments, erased, want, chunk_ids, version,
     want: subset of erased to rebuild.
     fmt: "moosefs" (default) or "interleaved" (no header or signature, each
       block preceded by its CRC; chunk_ids and version are unused there).
+    chunk_blocks: optional, S block counts in 1..1024: chunk s is that many
+      blocks long, so its part i has number_of_blocks(slice_type, i,
+      chunk_blocks[s]) blocks (slice_traits.h:311-316) and the fragments
+      are [S, Lmax] with rows read only that far.  Every returned image has
+      its own chunk's size — header + nb*65536 (MooseFS), nb*65540
+      (INTERLEAVED); a part of 0 blocks gives a header-only or empty image.
+      erased / want may then also be per-stripe sets
+      (ReedSolomon.recover_batch_ragged).
     Returns dict (chunk_index s, part_index) -> image tensor; image layout
     per chunkserver/chunk.cc (scrub.py geometry), CRC array filled by the
     GPU crc32_blocks kernel, signature per chunk_signature.cc:87-90.
@@ -74,6 +149,9 @@ def rebuild_part_images(k, m, fragments, erased, want, chunk_ids, version,
     slice_type = st.ec_slice_type(k, m)
     scrub.image_layout(fmt, slice_type)     # refuses an unknown fmt
     rs = ReedSolomon(k, m, device=device)
+    if chunk_blocks is not None:
+        return _rebuild_ragged(rs, slice_type, fragments, erased, want,
+                               chunk_ids, version, device, fmt, chunk_blocks)
     if fmt == "interleaved":
         return _rebuild_interleaved(rs, slice_type, fragments, erased, want,
                                     device)
