@@ -298,6 +298,54 @@ int lizec_ec_encode_batch_ragged(lizec_engine *e, int srcs, int dests,
                                  uint32_t src_block_stride,
                                  uint32_t dst_block_stride, void *stream);
 
+/* Batched EC over parts cut from a CHUNK VIEW: the ragged call above with
+ * the chunk's data, held in another slice type, as its source side.  This is
+ * how SliceRecoveryPlanner builds a part that its own slice cannot give
+ * (slice_recovery_planner.h:85-204), the path of every chunk when a goal
+ * changes (2 copies -> ec(8,2), ec(3,2) -> ec(8,2)): the chunk is read as
+ * consecutive blocks (chunk_read_planner.h:36-58), a data part of the target
+ * is every row_cols-th of them (kRecoverDataPart, :41-55), a parity part is
+ * computed over rows of row_cols consecutive ones (kRecoverParityPart,
+ * ec_read_plan.h:38-66, xor_read_plan.h:39).
+ *  gftbls, ntables, tbl_index, dst_dptrs, dst_nblocks, strides: as for
+ *             lizec_ec_encode_batch_ragged
+ *  view_dptrs : HOST array [num_stripes][view_parts]: address of block 0's
+ *             data of every data part of the SOURCE slice, in view-column
+ *             order (standard: the copy; xorN: parts 1..N; ec(k,m): parts
+ *             0..k-1)
+ *  view_parts : data parts of the source slice, 1..32; one value per call
+ *  chunk_blocks: HOST array [num_stripes]: n, the blocks of the chunk.
+ *             Chunk block c < n is the 64 KiB at
+ *             view[c % view_parts] + (c / view_parts) * src_block_stride;
+ *             blocks from n on count as zeros and no byte of them is read.
+ *             View address p is used iff p < n; an unused one may be 0.
+ *  row_cols   : data parts of the TARGET slice, 1..32
+ *  src_col0   : HOST array [num_stripes], or NULL = all 0.  In block row b
+ *             source j (the table's column j) is chunk block
+ *             b*row_cols + src_col0[s] + j.  A parity target has column 0 and
+ *             srcs = row_cols; a data target has its part index, srcs = 1 and
+ *             a table of coefficient 1.
+ * A destination block that no source reaches is written as zeros.  Whole
+ * chunks only: there is no starting row.
+ * Returns LIZEC_EINVAL from the host, with nothing enqueued, for everything
+ * the ragged call refuses about tables, destinations and strides, and if
+ * view_parts or row_cols is outside 1..32, src_col0[s] + srcs > row_cols,
+ * chunk_blocks[s] is 0 or above 1048576, or a used view address is 0 or not
+ * a multiple of 4.
+ * The source side keeps the aligned vector accesses if its stride and used
+ * view addresses are all multiples of 16.  There is no plan form.  Stream
+ * and thread contract as for the other batch calls. */
+int lizec_ec_encode_batch_view(lizec_engine *e, int srcs, int dests,
+                               const uint8_t *gftbls, int ntables,
+                               const uint32_t *tbl_index,
+                               const uint64_t *view_dptrs, int view_parts,
+                               const uint32_t *chunk_blocks, int row_cols,
+                               const uint32_t *src_col0,
+                               const uint64_t *dst_dptrs,
+                               const uint32_t *dst_nblocks, int num_stripes,
+                               uint32_t src_block_stride,
+                               uint32_t dst_block_stride, void *stream);
+
 /* The block map of a ragged batch; pure host code, needs no GPU.  One
  * entry (stripe, block) per 64 KiB block row: stripe s contributes blocks
  * 0 .. max_l dst_nblocks[s][l] - 1, stripe-major, ascending.

@@ -8,6 +8,8 @@ package is the host-side mirror of the reference's EC surfaces:
   lizardfs_amd.slice_traits — Goal::Slice::Type / ChunkPartType algebra
   lizardfs_amd.ec           — batched ReedSolomon encode/decode on GPU
   lizardfs_amd.crc          — per-block CRC32 (GPU batch + host scalar)
+  lizardfs_amd.convert      — parts of one slice type from a chunk held in
+                              another (goal change)
 
 PyTorch supplies device memory and streams only; all byte-level compute is
 the HIP library.  There is NO CPU fallback on the product path: using the

@@ -42,6 +42,7 @@
 #include "ec_kernel_multi.h"
 #include "ec_kernel_strided.h"
 #include "ec_kernel_ragged.h"
+#include "ec_kernel_view.h"
 #include "crc_fold.h"
 
 /* Product kernel configuration (chosen by the variant A/B harness,
@@ -1021,6 +1022,169 @@ extern "C" int lizec_ec_encode_batch_ragged(
 		default: LIZEC_LAUNCH_RAGGED_D(8); break;
 		}
 #undef LIZEC_LAUNCH_RAGGED_D
+		base += d;
+	}
+	LIZEC_CHECK(hipGetLastError());
+	return LIZEC_OK;
+}
+
+/* ------------------------------------------------------------------ */
+/* Chunk views: parts cut from a chunk held in another slice type     */
+/* (ec_kernel_view.h)                                                 */
+/* ------------------------------------------------------------------ */
+
+struct view_dev {
+	const uint8_t *tbls;
+	const uint32_t *index;
+	const uint2 *map;
+	const uint64_t *view, *dst;
+	const uint32_t *chunk_nb, *col0, *dst_nb;
+	uint32_t view_parts, row_cols;
+};
+
+/* One pass of the view kernel: the grid of launch_ec_ragged. */
+template <int D>
+static void launch_ec_view(uint32_t entries, int srcs, int dest_base,
+                           const view_dev &v, int dests_total,
+                           uint32_t src_stride, uint32_t dst_stride,
+                           bool sal, bool dal, hipStream_t s) {
+	constexpr int CH = ec_chunks_for(D);
+	uint32_t total_tiles = entries * (kECBlockBytes / (kChunkBytes * CH));
+	size_t lds = (size_t)D * srcs * kECTblBytes;
+#define LIZEC_LAUNCH_VIEW(SAL, DAL)                                         \
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(ec_encode_view_kernel<D, CH, SAL, DAL>), \
+	                   dim3(total_tiles), dim3(kThreads), lds, s, srcs,     \
+	                   dest_base, v.tbls, v.index, v.map, v.view,           \
+	                   v.view_parts, v.chunk_nb, v.row_cols, v.col0, v.dst, \
+	                   v.dst_nb, dests_total, src_stride, dst_stride)
+	if (sal && dal) LIZEC_LAUNCH_VIEW(true, true);
+	else if (sal) LIZEC_LAUNCH_VIEW(true, false);
+	else if (dal) LIZEC_LAUNCH_VIEW(false, true);
+	else LIZEC_LAUNCH_VIEW(false, false);
+#undef LIZEC_LAUNCH_VIEW
+}
+
+extern "C" int lizec_ec_encode_batch_view(
+    lizec_engine *e, int srcs, int dests, const uint8_t *gftbls, int ntables,
+    const uint32_t *tbl_index, const uint64_t *view_dptrs, int view_parts,
+    const uint32_t *chunk_blocks, int row_cols, const uint32_t *src_col0,
+    const uint64_t *dst_dptrs, const uint32_t *dst_nblocks, int num_stripes,
+    uint32_t src_block_stride, uint32_t dst_block_stride, void *stream) {
+	if (!e || !gftbls || !view_dptrs || !chunk_blocks || !dst_dptrs ||
+	    !dst_nblocks)
+		return LIZEC_EINVAL;
+	if (srcs < 1 || srcs > 32 || dests < 1 || dests > 32 || num_stripes < 1)
+		return LIZEC_EINVAL;
+	if (view_parts < 1 || view_parts > 32 || row_cols < 1 || row_cols > 32 ||
+	    srcs > row_cols)
+		return LIZEC_EINVAL;
+	if (ntables < 1 ||
+	    (uint64_t)ntables * 32 * srcs * dests > (uint64_t)1 << 30)
+		return LIZEC_EINVAL;
+	if (src_block_stride < kECBlockBytes || dst_block_stride < kECBlockBytes)
+		return LIZEC_EINVAL;
+	if (tbl_index)
+		for (int i = 0; i < num_stripes; ++i)
+			if (tbl_index[i] >= (uint32_t)ntables) return LIZEC_EINVAL;
+	size_t nview = (size_t)num_stripes * view_parts;
+	size_t ndst = (size_t)num_stripes * dests;
+	/* the source side's bits: the stride and the view addresses in use,
+	 * those of the parts that hold at least one block of their chunk */
+	uint64_t sbits = src_block_stride, dbits = dst_block_stride;
+	for (int i = 0; i < num_stripes; ++i) {
+		uint32_t n = chunk_blocks[i];
+		if (n == 0 || n > 1048576u) return LIZEC_EINVAL;
+		if (src_col0 && (uint64_t)src_col0[i] + srcs > (uint64_t)row_cols)
+			return LIZEC_EINVAL;
+		const uint64_t *vp = view_dptrs + (size_t)i * view_parts;
+		for (uint32_t p = 0; p < (uint32_t)view_parts && p < n; ++p) {
+			if (!vp[p]) return LIZEC_EINVAL;
+			sbits |= vp[p];
+		}
+	}
+	for (size_t i = 0; i < ndst; ++i) {
+		if (dst_nblocks[i] > 32768u) return LIZEC_EINVAL;
+		if (!dst_nblocks[i]) continue;
+		if (!dst_dptrs[i]) return LIZEC_EINVAL;
+		dbits |= dst_dptrs[i];
+	}
+	if ((sbits | dbits) & 3) return LIZEC_EINVAL;
+	const bool sal = (sbits & 15) == 0, dal = (dbits & 15) == 0;
+	int64_t entries =
+	    lizec_ragged_block_map(dst_nblocks, dests, num_stripes, nullptr, 0);
+	if (entries <= 0) return LIZEC_EINVAL;
+	hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+	LIZEC_CHECK(hipSetDevice(e->device));
+
+	/* the ragged call's scratch, with the chunk counts and first columns
+	 * where it keeps the source counts; every section 16-byte aligned */
+	auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+	size_t ntbl = (size_t)ntables * srcs * dests;   /* 32-byte tables */
+	size_t o_index = up16(ntbl * kECTblBytes);
+	size_t o_map = o_index + up16((size_t)num_stripes * 4);
+	size_t o_cnb = o_map + up16((size_t)entries * 8);
+	size_t o_col = o_cnb + up16((size_t)num_stripes * 4);
+	size_t o_dnb = o_col + up16((size_t)num_stripes * 4);
+	size_t bytes = o_dnb + up16(ndst * 4);
+	lizec_stream_ctx *c;
+	int r = ctx_acquire_ragged(e, s, nview + ndst, (nview + ndst) * 8, bytes,
+	                           &c);
+	if (r != LIZEC_OK) return r;
+	uint8_t *h = c->h_ragged;
+	for (size_t i = 0; i < ntbl; ++i)
+		pack_mixed_radix(gftbls + i * 32, h + i * kECTblBytes);
+	if (tbl_index)
+		memcpy(h + o_index, tbl_index, (size_t)num_stripes * 4);
+	else
+		memset(h + o_index, 0, (size_t)num_stripes * 4);
+	if (lizec_ragged_block_map(dst_nblocks, dests, num_stripes,
+	                           (uint32_t *)(h + o_map),
+	                           (uint64_t)entries) != entries)
+		return LIZEC_EINVAL;
+	memcpy(h + o_cnb, chunk_blocks, (size_t)num_stripes * 4);
+	if (src_col0)
+		memcpy(h + o_col, src_col0, (size_t)num_stripes * 4);
+	else
+		memset(h + o_col, 0, (size_t)num_stripes * 4);
+	memcpy(h + o_dnb, dst_nblocks, ndst * 4);
+	uint64_t *pstage = (uint64_t *)(c->h_staging + (size_t)kECTblBytes * 32 * 32);
+	memcpy(pstage, view_dptrs, nview * 8);
+	memcpy(pstage + nview, dst_dptrs, ndst * 8);
+	LIZEC_CHECK(hipMemcpyAsync(c->d_ragged, h, bytes, hipMemcpyHostToDevice, s));
+	LIZEC_CHECK(hipMemcpyAsync(c->d_ptrs, pstage, (nview + ndst) * 8,
+	                           hipMemcpyHostToDevice, s));
+	LIZEC_CHECK(hipEventRecord(c->uploaded, s));
+	c->ev_recorded = true;
+
+	view_dev vd;
+	vd.tbls = c->d_ragged;
+	vd.index = (const uint32_t *)(c->d_ragged + o_index);
+	vd.map = (const uint2 *)(c->d_ragged + o_map);
+	vd.chunk_nb = (const uint32_t *)(c->d_ragged + o_cnb);
+	vd.col0 = (const uint32_t *)(c->d_ragged + o_col);
+	vd.dst_nb = (const uint32_t *)(c->d_ragged + o_dnb);
+	vd.view = c->d_ptrs;
+	vd.dst = c->d_ptrs + nview;
+	vd.view_parts = (uint32_t)view_parts;
+	vd.row_cols = (uint32_t)row_cols;
+	/* passes of at most 8 destinations, as run_batch_strided */
+	for (int base = 0; base < dests;) {
+		int d = dests - base;
+		if (d > 8) d = 8;
+#define LIZEC_LAUNCH_VIEW_D(D)                                             \
+	launch_ec_view<D>((uint32_t)entries, srcs, base, vd, dests,            \
+	                  src_block_stride, dst_block_stride, sal, dal, s)
+		switch (d) {
+		case 1: LIZEC_LAUNCH_VIEW_D(1); break;
+		case 2: LIZEC_LAUNCH_VIEW_D(2); break;
+		case 3: LIZEC_LAUNCH_VIEW_D(3); break;
+		case 4: LIZEC_LAUNCH_VIEW_D(4); break;
+		case 5: LIZEC_LAUNCH_VIEW_D(5); break;
+		case 6: LIZEC_LAUNCH_VIEW_D(6); break;
+		case 7: LIZEC_LAUNCH_VIEW_D(7); break;
+		default: LIZEC_LAUNCH_VIEW_D(8); break;
+		}
+#undef LIZEC_LAUNCH_VIEW_D
 		base += d;
 	}
 	LIZEC_CHECK(hipGetLastError());

@@ -131,6 +131,11 @@ def lib():
         ctypes.c_void_p, ctypes.c_int, ctypes.c_int, u8p, ctypes.c_int, u32p,
         u64p, u32p, u64p, u32p, ctypes.c_int, ctypes.c_uint32,
         ctypes.c_uint32, ctypes.c_void_p]
+    L.lizec_ec_encode_batch_view.restype = ctypes.c_int
+    L.lizec_ec_encode_batch_view.argtypes = [
+        ctypes.c_void_p, ctypes.c_int, ctypes.c_int, u8p, ctypes.c_int, u32p,
+        u64p, ctypes.c_int, u32p, ctypes.c_int, u32p, u64p, u32p,
+        ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
     L.lizec_ragged_block_map.restype = ctypes.c_int64
     L.lizec_ragged_block_map.argtypes = [
         u32p, ctypes.c_int, ctypes.c_int, u32p, ctypes.c_uint64]

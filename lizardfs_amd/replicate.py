@@ -182,6 +182,71 @@ def rebuild_part_images(k, m, fragments, erased, want, chunk_ids, version,
     return out
 
 
+def convert_part_images(src_slice, fragments, chunk_blocks, target_slice,
+                        want, chunk_ids, version, fmt="moosefs",
+                        src_erased=None, src_stride=st.BLOCK_SIZE, device=0):
+    """convert.convert_parts straight into part images: the `want` parts of
+    `target_slice` for chunks held as `src_slice` (a goal change), each image
+    in on-disk format `fmt` and sized for its own chunk, recovered in place
+    by the view calls and its CRCs filled by lizec_crc_fill_batch_strided,
+    exactly as rebuild_part_images(chunk_blocks=...) does for a rebuild from
+    the part's own slice.
+
+    src_slice, fragments, chunk_blocks, target_slice, want, src_erased,
+    src_stride: as for convert_parts.  chunk_ids, version, fmt: as for
+    rebuild_part_images.
+    Returns dict (chunk_index s, target part) -> image tensor.
+    """
+    from . import convert
+    doff, coff, bstride, cstride = scrub.image_layout(fmt, target_slice)
+    plan = convert._prepare(src_slice, fragments, chunk_blocks, target_slice,
+                            want, src_erased, src_stride, device)
+    S, oc = plan.slots.shape
+    if fmt == "moosefs" and len(chunk_ids) != S:
+        raise ValueError("need one chunk id per chunk")
+    slots, dst_nb, dev = plan.slots, plan.dst_nb, plan.dev
+    # one arena; image (s, j) at offs[s, j], sized for its own block count
+    used = slots >= 0
+    head = doff if fmt == "moosefs" else 0
+    sizes = np.where(used, head + dst_nb.astype(np.int64) *
+                     (st.BLOCK_SIZE if fmt == "moosefs" else bstride), 0)
+    offs = np.concatenate([[0], np.cumsum(sizes.ravel())[:-1]]).reshape(S, oc)
+    arena = torch.empty(max(int(sizes.sum()), 1), dtype=torch.uint8,
+                        device=dev)
+    images = {}
+    pairs = [(s, j) for s in range(S) for j in range(oc) if used[s, j]]
+    for s, j in pairs:
+        images[(s, int(slots[s, j]))] = \
+            arena[int(offs[s, j]):int(offs[s, j] + sizes[s, j])]
+    if fmt == "moosefs":
+        hdrs = np.zeros((len(pairs), doff), np.uint8)
+        for n, (s, j) in enumerate(pairs):
+            sig = scrub.build_signature(int(chunk_ids[s]), version,
+                                        target_slice, int(slots[s, j]))
+            hdrs[n, :len(sig)] = np.frombuffer(sig, np.uint8)
+        hdrs = torch.from_numpy(hdrs).to(dev)
+        for n, (s, j) in enumerate(pairs):
+            images[(s, int(slots[s, j]))][:doff] = hdrs[n]
+    base = np.uint64(arena.data_ptr()) + offs.astype(np.uint64)
+    fill = [(s, j) for s, j in pairs if dst_nb[s, j]]
+    if fill:
+        plan.run(base + np.uint64(doff), bstride)
+        n = len(fill)
+        dptrs = np.array([base[s, j] for s, j in fill], np.uint64)
+        doffs = np.full(n, doff, np.uint32)
+        coffs = np.full(n, coff, np.uint32)
+        counts = np.array([dst_nb[s, j] for s, j in fill], np.uint32)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        L.check(L.lib().lizec_crc_fill_batch_strided(
+            L.engine(device),
+            dptrs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+            doffs.ctypes.data_as(u32p), coffs.ctypes.data_as(u32p),
+            counts.ctypes.data_as(u32p), n, bstride, cstride,
+            ctypes.c_void_p(stream)), "lizec_crc_fill_batch_strided")
+    return images
+
+
 def replicate_stream(k, m, host_parts, erased, want, chunk_ids, version,
                      out=None, device=0, sub_batch=0, fmt="moosefs"):
     """The full ChunkReplicator::replicate pipeline
