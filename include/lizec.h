@@ -394,7 +394,13 @@ int lizec_scrub_batch(lizec_engine *e, const uint64_t *chunk_dptrs,
  * its stored CRC at crc_offs[i] + b*crc_stride.  Covers both on-disk
  * formats: MooseFS (stride 65536 / 4; the wrapper above) and INTERLEAVED
  * (kHddBlockSize = 65540, chunk.h:40: 4-byte CRC inline before each
- * block — data_off 4, both strides 65540, crc_off 0). */
+ * block — data_off 4, both strides 65540, crc_off 0).  Block data must be
+ * 4-byte aligned (chunk_dptrs[i] + data_offs[i] and block_stride multiples
+ * of 4) and block_stride >= 65536; the stored CRC is read bytewise and needs
+ * no alignment.  The largest block count times either stride must not exceed
+ * 2^32-1.  Anything else, a NULL array, an address of 0 (also for an image
+ * of no blocks), or no blocks at all returns LIZEC_EINVAL with nothing
+ * enqueued; dev_status_out is not written. */
 int lizec_scrub_batch_strided(lizec_engine *e, const uint64_t *chunk_dptrs,
                               const uint32_t *data_offs,
                               const uint32_t *crc_offs,
@@ -407,8 +413,10 @@ int lizec_scrub_batch_strided(lizec_engine *e, const uint64_t *chunk_dptrs,
  * big-endian at crc_offs[i] + b*crc_stride; no other byte of an image is
  * written.  Arguments as above, without the status array.  Block data must
  * be 4-byte aligned (chunk_dptrs[i] + data_offs[i] and block_stride
- * multiples of 4) and block_stride >= 65536; anything else, an address of
- * 0, or no blocks at all returns LIZEC_EINVAL with nothing enqueued. */
+ * multiples of 4) and block_stride >= 65536, and the largest block count
+ * times either stride must not exceed 2^32-1; anything else, a NULL array,
+ * an address of 0, or no blocks at all returns LIZEC_EINVAL with nothing
+ * enqueued.  The two calls share these checks. */
 int lizec_crc_fill_batch_strided(lizec_engine *e, const uint64_t *chunk_dptrs,
                                  const uint32_t *data_offs,
                                  const uint32_t *crc_offs,

@@ -1639,25 +1639,52 @@ static int upload_image_meta(lizec_engine *e, hipStream_t s,
 	return LIZEC_OK;
 }
 
+/* Host checks shared by the scrub and the CRC fill, made before anything is
+ * allocated or enqueued; on success *max_blocks_out is the largest count. */
+static int check_image_args(const uint64_t *chunk_dptrs,
+                            const uint32_t *data_offs,
+                            const uint32_t *crc_offs,
+                            const uint32_t *block_counts, int nchunks,
+                            uint32_t block_stride, uint32_t crc_stride,
+                            uint32_t *max_blocks_out) {
+	if (!chunk_dptrs || !data_offs || !crc_offs || !block_counts ||
+	    nchunks < 1)
+		return LIZEC_EINVAL;
+	/* blocks are read in 32-bit words or wider, and must not overlap */
+	if (block_stride < 65536u || (block_stride & 3)) return LIZEC_EINVAL;
+	uint32_t max_blocks = 0;
+	for (int i = 0; i < nchunks; ++i) {
+		if (!chunk_dptrs[i] || ((chunk_dptrs[i] + data_offs[i]) & 3))
+			return LIZEC_EINVAL;
+		if (block_counts[i] > max_blocks) max_blocks = block_counts[i];
+	}
+	/* the kernel forms b*stride in 32 bits */
+	if (max_blocks == 0 ||
+	    (uint64_t)max_blocks * block_stride > 0xFFFFFFFFull ||
+	    (uint64_t)max_blocks * crc_stride > 0xFFFFFFFFull)
+		return LIZEC_EINVAL;
+	*max_blocks_out = max_blocks;
+	return LIZEC_OK;
+}
+
 extern "C" int lizec_scrub_batch_strided(
     lizec_engine *e, const uint64_t *chunk_dptrs, const uint32_t *data_offs,
     const uint32_t *crc_offs, const uint32_t *block_counts, int nchunks,
     uint32_t block_stride, uint32_t crc_stride, int32_t *dev_status_out,
     void *stream) {
-	if (!e || !chunk_dptrs || nchunks < 1 || !dev_status_out)
-		return LIZEC_EINVAL;
+	if (!e || !dev_status_out) return LIZEC_EINVAL;
+	uint32_t max_blocks = 0;
+	int r = check_image_args(chunk_dptrs, data_offs, crc_offs, block_counts,
+	                         nchunks, block_stride, crc_stride, &max_blocks);
+	if (r != LIZEC_OK) return r;
 	hipStream_t s = stream ? (hipStream_t)stream : e->stream;
 	LIZEC_CHECK(hipSetDevice(e->device));
 	uint64_t *d_ptrs;
 	uint32_t *d_doffs, *d_coffs, *d_counts;
-	int r = upload_image_meta(e, s, chunk_dptrs, data_offs, crc_offs,
-	                          block_counts, nchunks, &d_ptrs, &d_doffs,
-	                          &d_coffs, &d_counts);
+	r = upload_image_meta(e, s, chunk_dptrs, data_offs, crc_offs,
+	                      block_counts, nchunks, &d_ptrs, &d_doffs,
+	                      &d_coffs, &d_counts);
 	if (r != LIZEC_OK) return r;
-	uint32_t max_blocks = 0;
-	for (int i = 0; i < nchunks; ++i)
-		if (block_counts[i] > max_blocks) max_blocks = block_counts[i];
-	if (max_blocks == 0) return LIZEC_EINVAL;
 	/* INT32_MAX sentinel = clean */
 	LIZEC_CHECK(hipMemsetD32Async((hipDeviceptr_t)dev_status_out, 0x7FFFFFFF,
 	                              nchunks, s));
@@ -1697,29 +1724,18 @@ extern "C" int lizec_crc_fill_batch_strided(
     lizec_engine *e, const uint64_t *chunk_dptrs, const uint32_t *data_offs,
     const uint32_t *crc_offs, const uint32_t *block_counts, int nchunks,
     uint32_t block_stride, uint32_t crc_stride, void *stream) {
-	if (!e || !chunk_dptrs || !data_offs || !crc_offs || !block_counts ||
-	    nchunks < 1)
-		return LIZEC_EINVAL;
-	/* blocks are read in 32-bit words or wider, and must not overlap */
-	if (block_stride < 65536u || (block_stride & 3)) return LIZEC_EINVAL;
+	if (!e) return LIZEC_EINVAL;
 	uint32_t max_blocks = 0;
-	for (int i = 0; i < nchunks; ++i) {
-		if (!chunk_dptrs[i] || ((chunk_dptrs[i] + data_offs[i]) & 3))
-			return LIZEC_EINVAL;
-		if (block_counts[i] > max_blocks) max_blocks = block_counts[i];
-	}
-	/* the kernel forms b*stride in 32 bits */
-	if (max_blocks == 0 ||
-	    (uint64_t)max_blocks * block_stride > 0xFFFFFFFFull ||
-	    (uint64_t)max_blocks * crc_stride > 0xFFFFFFFFull)
-		return LIZEC_EINVAL;
+	int r = check_image_args(chunk_dptrs, data_offs, crc_offs, block_counts,
+	                         nchunks, block_stride, crc_stride, &max_blocks);
+	if (r != LIZEC_OK) return r;
 	hipStream_t s = stream ? (hipStream_t)stream : e->stream;
 	LIZEC_CHECK(hipSetDevice(e->device));
 	uint64_t *d_ptrs;
 	uint32_t *d_doffs, *d_coffs, *d_counts;
-	int r = upload_image_meta(e, s, chunk_dptrs, data_offs, crc_offs,
-	                          block_counts, nchunks, &d_ptrs, &d_doffs,
-	                          &d_coffs, &d_counts);
+	r = upload_image_meta(e, s, chunk_dptrs, data_offs, crc_offs,
+	                      block_counts, nchunks, &d_ptrs, &d_doffs,
+	                      &d_coffs, &d_counts);
 	if (r != LIZEC_OK) return r;
 	return image_crc_launch(e, d_ptrs, d_doffs, d_coffs, d_counts, nchunks,
 	                        max_blocks, block_stride, crc_stride, s);

@@ -26,6 +26,34 @@ def _tables_cache_key(k, m, present, nonnull, needed):
     return (k, m, present, nonnull, needed)
 
 
+# Plan-cache keys.  A cached plan holds device pointer arrays built from the
+# addresses, row strides and geometry of one call, so every number those
+# arrays (or the tables) are computed from must be part of the key.  Pure
+# functions of ints and tuples: no tensors, no engine.
+
+def enc_plan_key(data_addr, parity_addr, S, plen):
+    """encode_batch(data, parity=...): both tensors are contiguous, so the
+    two base addresses, S and plen fix every part address."""
+    return ("enc", int(data_addr), int(parity_addr), int(S), int(plen))
+
+
+def rec_plan_key(present, nonnull, needed, src_addrs, src_strides, out_addrs,
+                 S, plen):
+    """recover_batch(..., out=...): fragment j's row s lies at
+    src_addrs[j] + s*src_strides[j]; the outputs are contiguous."""
+    return ("rec", int(present), int(nonnull), int(needed),
+            tuple(int(a) for a in src_addrs),
+            tuple(int(x) for x in src_strides),
+            tuple(int(a) for a in out_addrs), int(S), int(plen))
+
+
+def mix_plan_key(digest, bases, strides, out_addr, S, plen):
+    """recover_batch_mixed(..., out=...): `digest` covers the per-stripe
+    patterns (table index, output slots, erased masks)."""
+    return ("mix", bytes(digest), tuple(int(b) for b in bases),
+            tuple(int(x) for x in strides), int(out_addr), int(S), int(plen))
+
+
 _POPCOUNT8 = np.array([bin(i).count("1") for i in range(256)], np.int64)
 
 
@@ -286,7 +314,7 @@ class ReedSolomon:
         dst = (parity.data_ptr() +
                np.arange(S * self.m, dtype=np.uint64) * np.uint64(plen))
         # plans are cached only for caller-owned (stable) output buffers
-        plan_key = (("enc", data.data_ptr(), parity.data_ptr(), S, plen)
+        plan_key = (enc_plan_key(data.data_ptr(), parity.data_ptr(), S, plen)
                     if caller_parity else None)
         self._run(plen, tbl, ic, oc, src, dst, S, plan_key=plan_key)
         return parity
@@ -356,18 +384,17 @@ class ReedSolomon:
                     for i in sorted(want)}
         rows = np.arange(S, dtype=np.uint64)
         src = np.empty((S, ic), np.uint64)
+        rstrides = [self._frag_geom(t, "fragment")[2] for t in srcs]
         for j, t in enumerate(srcs):
-            _, _, rstride = self._frag_geom(t, "fragment")
-            src[:, j] = t.data_ptr() + rows * np.uint64(rstride)
+            src[:, j] = t.data_ptr() + rows * np.uint64(rstrides[j])
         dst = np.empty((S, oc), np.uint64)
         for j, i in enumerate(sorted(want)):
             dst[:, j] = outs[i].data_ptr() + rows * np.uint64(plen)
         plan_key = None
         if out is not None:
-            plan_key = ("rec", present, nonnull, needed,
-                        tuple(t.data_ptr() for t in srcs),
-                        tuple(outs[i].data_ptr() for i in sorted(want)),
-                        S, plen)
+            plan_key = rec_plan_key(
+                present, nonnull, needed, [t.data_ptr() for t in srcs],
+                rstrides, [outs[i].data_ptr() for i in sorted(want)], S, plen)
         self._run(plen, tbl, ic, oc, np.ascontiguousarray(src.ravel()),
                   np.ascontiguousarray(dst.ravel()), S, plan_key=plan_key)
         return outs
@@ -553,8 +580,8 @@ class ReedSolomon:
         h.update(index.tobytes())
         h.update(pslots.tobytes())
         h.update(pemask.tobytes())
-        plan_key = ("mix", h.digest(), tuple(int(b) for b in bases),
-                    tuple(int(x) for x in strides), outs.data_ptr(), S, plen)
+        plan_key = mix_plan_key(h.digest(), bases, strides, outs.data_ptr(),
+                                S, plen)
         plan = self._plans.get(plan_key)
         if plan is None:
             while len(self._plans) >= 64:   # bound device-side state

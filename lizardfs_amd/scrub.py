@@ -132,8 +132,15 @@ def _scrub_group(idx, images, fmts, device, results):
             doffs[j] = hdr
             coffs[j] = SIGNATURE_BLOCK
             counts[j] = (img.numel() - hdr) // st.BLOCK_SIZE
-    if counts.max(initial=0) == 0:
+    # an image of no blocks is clean, and an empty tensor has address 0,
+    # which the call refuses: only images with blocks are passed on
+    keep = np.flatnonzero(counts)
+    if keep.size == 0:
         return
+    idx = [idx[j] for j in keep]
+    dptrs, doffs, coffs, counts = (np.ascontiguousarray(a[keep]) for a in
+                                   (dptrs, doffs, coffs, counts))
+    n = len(idx)
     status = torch.empty(n, dtype=torch.int32, device=f"cuda:{device}")
     stream = torch.cuda.current_stream(device).cuda_stream
     L.check(L.lib().lizec_scrub_batch_strided(
