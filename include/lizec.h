@@ -375,6 +375,31 @@ int lizec_crc32_batch(lizec_engine *e, const void *dev_buf, uint32_t block_len,
                       uint64_t nblocks, uint32_t seed, uint32_t *dev_crcs_out,
                       void *stream);
 
+/* CRC32 of n independent byte ranges:
+ *  dev_crcs_out[i] = lizec_crc32(seed, dptrs[i], lens[i])
+ * The ranges hdd_write hashes (hddspacemgr.cc:1918, :1951-1953) and the
+ * client's write path produces (write_executor.cc:94-102): any length up to
+ * a block, at any byte address.  One launch per call, one wave per range.
+ *  dptrs : HOST array of n device addresses, of ANY byte alignment
+ *  lens  : HOST array of n lengths, 0..65536 (the reference's
+ *          LIZARDFS_ERROR_WRONGSIZE bound); a length of 0 gives `seed`, and
+ *          its address is not used and may be 0
+ *  dev_crcs_out: device u32[n], host-order values as for lizec_crc32_batch
+ * Ranges may overlap or repeat.  No byte outside [dptrs[i], dptrs[i] +
+ * lens[i]) is read: the bytes before the first and behind the last 16-byte
+ * boundary inside a range are loaded one at a time, the aligned middle in
+ * 16-byte vectors (folded 16 bytes per step from the first whole aligned
+ * unit on; csrc/crc_ranges.h).  The launch has at most 16384 workgroups of
+ * 4 waves; beyond 65536 ranges every wave takes several.
+ * Returns LIZEC_EINVAL from the host, with nothing enqueued and
+ * dev_crcs_out not written, for a NULL array, n == 0 or n > 2^24, a length
+ * above 65536, or a non-zero length with address 0.  Stream and thread
+ * contract as for the other batch calls (the tables travel through the
+ * stream's call scratch). */
+int lizec_crc32_ranges(lizec_engine *e, const uint64_t *dptrs,
+                       const uint32_t *lens, uint32_t n, uint32_t seed,
+                       uint32_t *dev_crcs_out, void *stream);
+
 /* Batched chunk scrub — hdd_int_test semantics (hddspacemgr.cc:2148-2212)
  * over MooseFS-format chunk-part images (chunk.cc:126-188: 1 KiB signature
  * block, big-endian u32 CRC array at crc_off, 64 KiB blocks at data_off):
@@ -423,6 +448,78 @@ int lizec_crc_fill_batch_strided(lizec_engine *e, const uint64_t *chunk_dptrs,
                                  const uint32_t *block_counts, int nchunks,
                                  uint32_t block_stride, uint32_t crc_stride,
                                  void *stream);
+
+/* The batched write gate — what hdd_write (hddspacemgr.cc:1899-2009) checks
+ * and computes before it touches the disk, for n writes at once.  One op is
+ * one packet: `size` bytes for [offset, offset + size) of one 64 KiB block. */
+typedef struct lizec_write_op {   /* 40 bytes, no padding */
+	uint64_t data;    /* device address of the `size` bytes to write */
+	uint64_t block;   /* device address of the block's current 65536 bytes;
+	                     0 = block at or past the end of the chunk */
+	uint64_t stored;  /* device address of the block's stored CRC, 4 bytes
+	                     big-endian, read bytewise (as the scrub does) */
+	uint32_t offset, size;
+	uint32_t crc;     /* the CRC the client claims for data */
+	uint32_t reserved;/* 0 */
+} lizec_write_op;
+
+enum { LIZEC_GATE_OK = 0, LIZEC_GATE_BAD_DATA = 1, LIZEC_GATE_BAD_BLOCK = 2 };
+enum { LIZEC_GATE_SPARSE = 1 };
+
+/* Per op, line for line after hdd_write:
+ *  - crc != crc32(0, data, size): LIZEC_GATE_BAD_DATA (:1918); nothing else
+ *    decides that op's outputs.
+ *  - offset == 0 && size == 65536: newcrc = crc (:1922-1941); block and
+ *    stored are ignored and may be 0.
+ *  - partial write, block == 0: the block counts as zeros (:1973-1991),
+ *    pre = zeroblock(0, offset), post = zeroblock(0, 65536-offset-size); no
+ *    stored CRC is read.
+ *  - partial write, block != 0: pre, changed and post are the CRCs of
+ *    block[0, offset), block[offset, offset+size) and the rest, combined as
+ *    :1954-1962 does (lizec_crc32_splice, with its offset == 0 branch and
+ *    the post step skipped when the range ends the block); a result other
+ *    than the stored CRC gives LIZEC_GATE_BAD_BLOCK (:1965).
+ *  - flags & LIZEC_GATE_SPARSE: a block whose four stored bytes are zero
+ *    and whose 65536 bytes are all zero (tested on the bytes, not by CRC)
+ *    counts as stored = zeroblock(0, 65536) — the INTERLEAVED read path's
+ *    rule (hddspacemgr.cc:1779, crc.cc:235-243).  Without the flag it does
+ *    not apply (MooseFS format, :1751).
+ *  - on LIZEC_GATE_OK, newcrc = splice(pre, offset, crc, size, post, 65536)
+ *    (:1992-2001); otherwise newcrc = 0.  size == 0 is legal and comes out
+ *    as the same algebra gives.
+ * The gate writes nothing but its two outputs: copying the data in and
+ * storing newcrc stay with the caller.
+ *  ops            : HOST array of n ops
+ *  dev_status_out : device int32[n], LIZEC_GATE_*
+ *  dev_newcrc_out : device u32[n]
+ * Two launches: lizec_crc32_ranges' kernel over four range slots per op
+ * (data, pre, changed, post; a slot an op does not need has length 0),
+ * carrying an OR of the bytes it reads for the sparse rule, then a
+ * finishing kernel, one thread per op, that combines, compares and writes
+ * the outputs.  The ranges are hashed before any data CRC is known, so the
+ * block of an op that ends as BAD_DATA is read too.  Op and range tables
+ * travel through the stream's call scratch; stream and thread contract as
+ * for the other batch calls.
+ * Scratch cost: 120 bytes of device scratch and 88 bytes of pinned host
+ * staging per op.  Both grow by doubling and stay with the stream's scratch
+ * until the engine is destroyed, so choose n by that and not by the bound
+ * below: 2^24 ops in one call hold about 2 GiB of each, 2^16 ops 8 MiB of
+ * each.  (lizec_crc32_ranges: 12 bytes of each per range.)
+ * Returns LIZEC_EINVAL from the host, with nothing enqueued and the outputs
+ * not written, for a NULL array, n == 0 or n > 2^24, size > 65536,
+ * offset >= 65536, offset + size > 65536, reserved != 0, size > 0 with
+ * data == 0, a partial op with block != 0 and stored == 0, or an unknown
+ * flag bit. */
+int lizec_write_gate_batch(lizec_engine *e, const lizec_write_op *ops,
+                           uint32_t n, uint32_t flags,
+                           int32_t *dev_status_out, uint32_t *dev_newcrc_out,
+                           void *stream);
+
+/* The same gate on the host: the addresses in ops are HOST addresses, the
+ * outputs host arrays, and no GPU is needed.  Same refusals (outputs not
+ * written), same results bit for bit. */
+int lizec_write_gate_host(const lizec_write_op *ops, uint32_t n,
+                          uint32_t flags, int32_t *status, uint32_t *newcrc);
 
 /* Pinned host memory for the streaming APIs (hipHostMalloc/hipHostFree):
  * pageable buffers work too but degrade the pipeline to synchronous

@@ -10,6 +10,8 @@ package is the host-side mirror of the reference's EC surfaces:
   lizardfs_amd.crc          — per-block CRC32 (GPU batch + host scalar)
   lizardfs_amd.convert      — parts of one slice type from a chunk held in
                               another (goal change)
+  lizardfs_amd.writegate    — the batched hdd_write gate: byte-range data
+                              and block CRC checks, new block CRCs
 
 PyTorch supplies device memory and streams only; all byte-level compute is
 the HIP library.  There is NO CPU fallback on the product path: using the
@@ -20,5 +22,7 @@ from .lib import LizecError, gpu_count  # noqa: F401
 from .lib import lib as load_lib  # noqa: F401
 from . import ec  # noqa: F401
 from . import crc  # noqa: F401
+from . import writegate  # noqa: F401
 
-__all__ = ["slice_traits", "ec", "crc", "load_lib", "gpu_count", "LizecError"]
+__all__ = ["slice_traits", "ec", "crc", "writegate", "load_lib", "gpu_count",
+           "LizecError"]

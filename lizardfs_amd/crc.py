@@ -58,3 +58,57 @@ def crc32_blocks(buf, block_len=slice_traits.BLOCK_SIZE, seed=0, out=None,
         ctypes.c_uint32(seed), ctypes.c_void_p(out.data_ptr()),
         ctypes.c_void_p(stream)), "lizec_crc32_batch")
     return out
+
+
+# lizec_crc32_ranges: a range is at most a block, a call at most 2^24
+# ranges; its launch has at most 16384 workgroups of 4 waves, one range per
+# wave at a time (lizec.h)
+MAX_RANGE_LEN = slice_traits.BLOCK_SIZE
+MAX_RANGES = 1 << 24
+RANGES_GRID_WAVES = 16384 * 4
+
+
+def crc32_ranges(buf, offsets, lengths, seed=0, out=None):
+    """CRC32 of independent byte ranges of a device buffer:
+    out[i] = crc32(seed, buf[offsets[i] : offsets[i] + lengths[i]]).
+
+    buf: contiguous uint8 CUDA tensor, of any alignment.  offsets, lengths:
+    integer arrays of equal size; a length is 0..65536 and a range of any
+    byte alignment, but inside buf (checked here, on the host).  Ranges may
+    overlap or repeat.  Returns an int32 CUDA tensor [n] holding the CRCs
+    (bit pattern; view as uint32), as crc32_blocks does.  No ranges at all
+    (n = 0) give an empty tensor without a call into the library.
+    """
+    if buf.dtype != torch.uint8 or not buf.is_cuda or not buf.is_contiguous():
+        raise ValueError("buf must be a contiguous CUDA uint8 tensor")
+    offs = np.asarray(offsets)
+    lens = np.asarray(lengths)
+    if offs.ndim != 1 or offs.shape != lens.shape or \
+            offs.dtype.kind not in "iu" or lens.dtype.kind not in "iu":
+        raise ValueError("offsets and lengths must be integer arrays of one "
+                         "size")
+    offs = offs.astype(np.int64)
+    lens = lens.astype(np.int64)
+    if (offs < 0).any() or (lens < 0).any() or \
+            (offs + lens > buf.numel()).any():
+        raise ValueError("a range lies outside buf")
+    if (lens > MAX_RANGE_LEN).any():
+        raise ValueError(f"a range is longer than {MAX_RANGE_LEN} bytes")
+    n = int(offs.size)
+    dev = buf.device.index or 0
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=buf.device)
+    elif out.dtype != torch.int32 or not out.is_cuda or \
+            not out.is_contiguous() or out.numel() != n:
+        raise ValueError("out must be a contiguous CUDA int32 tensor [n]")
+    if n == 0:
+        return out            # the library refuses an empty call
+    dptrs = (offs + buf.data_ptr()).astype(np.uint64)
+    lens32 = lens.astype(np.uint32)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    L.check(L.lib().lizec_crc32_ranges(
+        L.engine(dev), dptrs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+        lens32.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), n,
+        ctypes.c_uint32(seed), ctypes.c_void_p(out.data_ptr()),
+        ctypes.c_void_p(stream)), "lizec_crc32_ranges")
+    return out

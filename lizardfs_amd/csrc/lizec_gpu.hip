@@ -44,6 +44,7 @@
 #include "ec_kernel_ragged.h"
 #include "ec_kernel_view.h"
 #include "crc_fold.h"
+#include "crc_ranges.h"
 
 /* Product kernel configuration (chosen by the variant A/B harness,
  * bench_variants.hip; numbers in profiles/ROUND1.md + ROUND2.md):
@@ -1604,6 +1605,124 @@ extern "C" int lizec_crc32_batch(lizec_engine *e, const void *dev_buf,
 		                   dim3(grid), dim3(kThreads), 0, s,
 		                   (const uint8_t *)dev_buf, block_len, nblocks,
 		                   seed, e->d_crc_const, dev_crcs_out);
+	LIZEC_CHECK(hipGetLastError());
+	return LIZEC_OK;
+}
+
+/* ------------------------------------------------------------------ */
+/* Byte-range CRC and the write gate (crc_ranges.h)                   */
+/* ------------------------------------------------------------------ */
+
+static_assert(kCrcRangesMats <= kCrcMatCount, "matrix bank too short");
+static_assert(sizeof(lizec_write_op) == 40, "lizec_write_op has padding");
+
+constexpr uint32_t kCrcRangesMaxN = 1u << 24;
+constexpr uint32_t kCrcRangesMaxGrid = 16384;   /* x 4 waves (lizec.h) */
+
+/* One wave per range over device-resident tables; d_nz = nullptr for the
+ * plain form, else the per-range "holds a non-zero byte" words. */
+static int launch_crc_ranges(lizec_engine *e, const uint64_t *d_addrs,
+                             const uint32_t *d_lens, uint32_t n, uint32_t seed,
+                             uint32_t *d_out, uint32_t *d_nz, hipStream_t s) {
+	uint32_t groups = (n + 3) / 4;
+	uint32_t grid = groups < kCrcRangesMaxGrid ? groups : kCrcRangesMaxGrid;
+	if (d_nz)
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(crc32_ranges_kernel<true>),
+		                   dim3(grid), dim3(kCrcRangesThreads), 0, s, d_addrs,
+		                   d_lens, n, seed, e->d_crc_const,
+		                   e->d_crc_const + kCrcTabWords, d_out, d_nz);
+	else
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(crc32_ranges_kernel<false>),
+		                   dim3(grid), dim3(kCrcRangesThreads), 0, s, d_addrs,
+		                   d_lens, n, seed, e->d_crc_const,
+		                   e->d_crc_const + kCrcTabWords, d_out, nullptr);
+	LIZEC_CHECK(hipGetLastError());
+	return LIZEC_OK;
+}
+
+extern "C" int lizec_crc32_ranges(lizec_engine *e, const uint64_t *dptrs,
+                                  const uint32_t *lens, uint32_t n,
+                                  uint32_t seed, uint32_t *dev_crcs_out,
+                                  void *stream) {
+	if (!e || !dptrs || !lens || !dev_crcs_out || n == 0 ||
+	    n > kCrcRangesMaxN)
+		return LIZEC_EINVAL;
+	for (uint32_t i = 0; i < n; ++i)
+		if (lens[i] > kCrcRangeMaxLen || (lens[i] && !dptrs[i]))
+			return LIZEC_EINVAL;
+	hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+	LIZEC_CHECK(hipSetDevice(e->device));
+	/* scratch (u64 slots reused): [addrs u64 x n][lens u32 x n] */
+	size_t slots = (size_t)n + ((size_t)n + 1) / 2;
+	lizec_stream_ctx *c;
+	int r = ctx_acquire(e, s, slots, slots * 8, &c);
+	if (r != LIZEC_OK) return r;
+	uint8_t *st = c->h_staging + (size_t)kECTblBytes * 32 * 32;
+	memcpy(st, dptrs, (size_t)n * 8);
+	memcpy(st + (size_t)n * 8, lens, (size_t)n * 4);
+	LIZEC_CHECK(hipMemcpyAsync(c->d_ptrs, st, (size_t)n * 12,
+	                           hipMemcpyHostToDevice, s));
+	LIZEC_CHECK(hipEventRecord(c->uploaded, s));
+	c->ev_recorded = true;
+	return launch_crc_ranges(e, c->d_ptrs, (const uint32_t *)(c->d_ptrs + n), n,
+	                         seed, dev_crcs_out, nullptr, s);
+}
+
+extern "C" int lizec_impl_write_gate_check(const lizec_write_op *ops,
+                                           uint32_t n, uint32_t flags);
+
+extern "C" int lizec_write_gate_batch(lizec_engine *e,
+                                      const lizec_write_op *ops, uint32_t n,
+                                      uint32_t flags, int32_t *dev_status_out,
+                                      uint32_t *dev_newcrc_out, void *stream) {
+	if (!e || !dev_status_out || !dev_newcrc_out) return LIZEC_EINVAL;
+	int r = lizec_impl_write_gate_check(ops, n, flags);
+	if (r != LIZEC_OK) return r;
+	hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+	LIZEC_CHECK(hipSetDevice(e->device));
+	/* scratch, in u64 slots: [ops 5n][range addrs 4n][range lens 2n] are
+	 * uploaded; [range crcs 2n][range non-zero words 2n] are the ranges
+	 * pass's outputs, read by the finishing kernel */
+	const size_t N = n;
+	lizec_stream_ctx *c;
+	r = ctx_acquire(e, s, 15 * N, 11 * N * 8, &c);
+	if (r != LIZEC_OK) return r;
+	uint8_t *st = c->h_staging + (size_t)kECTblBytes * 32 * 32;
+	memcpy(st, ops, N * sizeof(lizec_write_op));
+	uint64_t *addrs = (uint64_t *)(st + 5 * N * 8);
+	uint32_t *lens = (uint32_t *)(st + 9 * N * 8);
+	for (size_t i = 0; i < N; ++i) {
+		const lizec_write_op &op = ops[i];
+		/* four slots per op: data, pre, changed, post; the block's three
+		 * only for a partial write into an existing block */
+		const bool blk =
+		    op.block != 0 && !(op.offset == 0 && op.size == 65536u);
+		const uint32_t end = op.offset + op.size;
+		addrs[4 * i] = op.data;
+		lens[4 * i] = op.size;
+		addrs[4 * i + 1] = blk ? op.block : 0;
+		lens[4 * i + 1] = blk ? op.offset : 0;
+		addrs[4 * i + 2] = blk ? op.block + op.offset : 0;
+		lens[4 * i + 2] = blk ? op.size : 0;
+		addrs[4 * i + 3] = blk ? op.block + end : 0;
+		lens[4 * i + 3] = blk ? 65536u - end : 0;
+	}
+	LIZEC_CHECK(hipMemcpyAsync(c->d_ptrs, st, 11 * N * 8,
+	                           hipMemcpyHostToDevice, s));
+	LIZEC_CHECK(hipEventRecord(c->uploaded, s));
+	c->ev_recorded = true;
+	const lizec_write_op *d_ops = (const lizec_write_op *)c->d_ptrs;
+	const uint64_t *d_addrs = c->d_ptrs + 5 * N;
+	const uint32_t *d_lens = (const uint32_t *)(c->d_ptrs + 9 * N);
+	uint32_t *d_crcs = (uint32_t *)(c->d_ptrs + 11 * N);
+	uint32_t *d_nz = (uint32_t *)(c->d_ptrs + 13 * N);
+	r = launch_crc_ranges(e, d_addrs, d_lens, 4 * n, 0u, d_crcs, d_nz, s);
+	if (r != LIZEC_OK) return r;
+	hipLaunchKernelGGL(write_gate_finish_kernel,
+	                   dim3((n + kCrcRangesThreads - 1) / kCrcRangesThreads),
+	                   dim3(kCrcRangesThreads), 0, s, d_ops, n, flags, d_crcs,
+	                   d_nz, e->d_crc_const + kCrcTabWords, dev_status_out,
+	                   dev_newcrc_out);
 	LIZEC_CHECK(hipGetLastError());
 	return LIZEC_OK;
 }

@@ -396,6 +396,74 @@ extern "C" void lizec_recompute_crc_if_block_empty(const uint8_t *block,
 	*crc = lizec_crc32_zeroblock(0, block_len);
 }
 
+/* The host checks of the write gate, shared by lizec_write_gate_host and
+ * lizec_write_gate_batch (lizec_gpu.hip): hdd_write's own bounds
+ * (hddspacemgr.cc:1912-1917) plus what an address table can get wrong. */
+extern "C" int lizec_impl_write_gate_check(const lizec_write_op *ops,
+                                           uint32_t n, uint32_t flags) {
+	if (!ops || n == 0 || n > (1u << 24)) return LIZEC_EINVAL;
+	if (flags & ~(uint32_t)LIZEC_GATE_SPARSE) return LIZEC_EINVAL;
+	for (uint32_t i = 0; i < n; ++i) {
+		const lizec_write_op &op = ops[i];
+		if (op.size > 65536u || op.offset >= 65536u ||
+		    op.offset + op.size > 65536u || op.reserved != 0)
+			return LIZEC_EINVAL;
+		if (op.size > 0 && op.data == 0) return LIZEC_EINVAL;
+		const bool full = op.offset == 0 && op.size == 65536u;
+		if (!full && op.block != 0 && op.stored == 0) return LIZEC_EINVAL;
+	}
+	return LIZEC_OK;
+}
+
+/* hdd_write's checks and CRC algebra (hddspacemgr.cc:1918-2001) over host
+ * memory; see lizec.h. */
+extern "C" int lizec_write_gate_host(const lizec_write_op *ops, uint32_t n,
+                                     uint32_t flags, int32_t *status,
+                                     uint32_t *newcrc) {
+	if (!status || !newcrc) return LIZEC_EINVAL;
+	int r = lizec_impl_write_gate_check(ops, n, flags);
+	if (r != LIZEC_OK) return r;
+	for (uint32_t i = 0; i < n; ++i) {
+		const lizec_write_op &op = ops[i];
+		status[i] = LIZEC_GATE_OK;
+		newcrc[i] = 0;
+		if (op.crc != lizec_crc32(0, (const uint8_t *)(uintptr_t)op.data,
+		                          op.size)) {
+			status[i] = LIZEC_GATE_BAD_DATA;
+			continue;
+		}
+		if (op.offset == 0 && op.size == 65536u) {
+			newcrc[i] = op.crc;
+			continue;
+		}
+		const uint32_t end = op.offset + op.size, rest = 65536u - end;
+		uint32_t pre, post;
+		if (op.block == 0) {
+			pre = lizec_crc32_zeroblock(0, op.offset);
+			post = lizec_crc32_zeroblock(0, rest);
+		} else {
+			const uint8_t *b = (const uint8_t *)(uintptr_t)op.block;
+			const uint8_t *p = (const uint8_t *)(uintptr_t)op.stored;
+			pre = lizec_crc32(0, b, op.offset);
+			post = lizec_crc32(0, b + end, rest);
+			uint32_t have = lizec_crc32_splice(
+			    pre, op.offset, lizec_crc32(0, b + op.offset, op.size),
+			    op.size, post, 65536u);
+			uint32_t stored = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) |
+			                  ((uint32_t)p[2] << 8) | p[3];
+			if (flags & LIZEC_GATE_SPARSE)
+				lizec_recompute_crc_if_block_empty(b, 65536u, &stored);
+			if (stored != have) {
+				status[i] = LIZEC_GATE_BAD_BLOCK;
+				continue;
+			}
+		}
+		newcrc[i] = lizec_crc32_splice(pre, op.offset, op.crc, op.size, post,
+		                               65536u);
+	}
+	return LIZEC_OK;
+}
+
 /* C++-linkage aliases so a LizardFS build linking against common/crc.h's
  * mangled symbols (crc.h:25-31) resolves them from this library. */
 uint32_t mycrc32(uint32_t crc, const uint8_t *block, uint32_t leng) {

@@ -150,6 +150,18 @@ def lib():
         ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, u8p,
         ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
         ctypes.c_int, ctypes.c_int]
+    L.lizec_crc32_ranges.restype = ctypes.c_int
+    L.lizec_crc32_ranges.argtypes = [
+        ctypes.c_void_p, u64p, u32p, ctypes.c_uint32, ctypes.c_uint32,
+        ctypes.c_void_p, ctypes.c_void_p]
+    L.lizec_write_gate_batch.restype = ctypes.c_int
+    L.lizec_write_gate_batch.argtypes = [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.lizec_write_gate_host.restype = ctypes.c_int
+    L.lizec_write_gate_host.argtypes = [
+        ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+        ctypes.c_void_p]
     _lib = L
     return _lib
 
