@@ -521,6 +521,75 @@ int lizec_write_gate_batch(lizec_engine *e, const lizec_write_op *ops,
 int lizec_write_gate_host(const lizec_write_op *ops, uint32_t n,
                           uint32_t flags, int32_t *status, uint32_t *newcrc);
 
+/* The batched read gate — what hdd_read (hddspacemgr.cc:1662-1727) does
+ * with one block through hdd_read_crc_and_block (:1525-1608), for n reads at
+ * once.  One op is one READ of `size` bytes at `offset` inside one 64 KiB
+ * block; its result is the payload of cstocl READ_DATA:
+ * [4-byte big-endian CRC][the bytes]. */
+typedef struct lizec_read_op {   /* 32 bytes, no padding */
+	uint64_t block;   /* device address of the block's 65536 bytes;
+	                     0 = block at or past the end of the chunk */
+	uint64_t stored;  /* address of its stored CRC, 4 bytes big-endian, read
+	                     bytewise */
+	uint64_t out;     /* address of the packet: 4 + size bytes are written */
+	uint32_t offset, size;
+} lizec_read_op;
+
+/* Per op, line for line after hdd_read / hdd_read_crc_and_block:
+ *  - block == 0 (:1535-1541, blocknum >= c->blocks): the packet's CRC is
+ *    zeroblock(0, size) — emptyblockcrc for a whole block — and its data
+ *    `size` zero bytes; status LIZEC_GATE_OK; stored is ignored.
+ *  - otherwise have = the CRC of block[0, 65536), spliced (as
+ *    lizec_crc32_splice does) from pre = block[0, offset),
+ *    mid = block[offset, offset + size) and post = the rest.
+ *    Without LIZEC_GATE_SPARSE (MooseFS format, :1547-1555): stored != have
+ *    gives LIZEC_GATE_BAD_BLOCK (the reference's ERROR_CRC).
+ *    With LIZEC_GATE_SPARSE (INTERLEAVED format, :1556-1596): a block whose
+ *    four stored bytes are all zero is NOT checked (:1571-1587 never calls
+ *    checkCRC there); its CRC counts as emptyblockcrc if its 65536 bytes
+ *    are all zero (tested on the bytes, not by CRC) and as 0 otherwise.
+ *    Stored bytes that are not all zero are checked as for MooseFS.
+ *  - on LIZEC_GATE_OK the packet's CRC is the block's CRC as just
+ *    determined when offset == 0 && size == 65536 (:1711-1712 passes the
+ *    stored value through, recomputing nothing), and crc32(0, block +
+ *    offset, size) for any other range (:1718); the data is the range.
+ *  - on LIZEC_GATE_BAD_BLOCK the four CRC bytes are written as 0 and the
+ *    data bytes as read: the reference, too, copies before it checks, and
+ *    the verdict is known only after the pass.  Send no such packet.
+ * Nothing outside [out, out + 4 + size) and dev_status_out[i] is written;
+ * no byte outside [block, block + 65536) and the four stored bytes is read.
+ * block and out may have ANY byte alignment.  Blocks may overlap or repeat
+ * between ops; packets must not overlap each other or any block or stored
+ * CRC of the call — otherwise the result is undefined.
+ *  ops            : HOST array of n ops
+ *  flags          : 0 or LIZEC_GATE_SPARSE, for the whole call
+ *  dev_status_out : device int32[n], LIZEC_GATE_OK or LIZEC_GATE_BAD_BLOCK
+ * One launch: one wave per op reads the block once, hashing pre, mid and
+ * post, storing mid to out + 4 from the registers it is hashed from, then
+ * splices, compares and writes CRC bytes and status (csrc/read_gate.h).  The
+ * stores are 16 bytes wide when (out + 4 - block - offset) is a multiple of
+ * 16, 16-byte vectors at 4-byte alignment when it is a multiple of 4, single
+ * bytes otherwise: a packet that is itself 16-byte aligned takes the second
+ * form for a 16-byte aligned block; align out + 4 with block + offset for
+ * the first.  At most 16384 workgroups of 4 waves; beyond 65536 ops every
+ * wave takes several.  The op table travels through the stream's call
+ * scratch; stream and thread contract as for the other batch calls.
+ * Scratch cost: 32 bytes of device scratch and 32 bytes of pinned host
+ * staging per op, kept with the stream's scratch as for the write gate.
+ * Returns LIZEC_EINVAL from the host, with nothing enqueued and no output
+ * written, for a NULL array, n == 0 or n > 2^24, size == 0 or offset + size
+ * > 65536 (hdd_read's ERROR_WRONGSIZE, :1669), offset >= 65536, out == 0,
+ * block != 0 with stored == 0, or an unknown flag bit. */
+int lizec_read_gate_batch(lizec_engine *e, const lizec_read_op *ops,
+                          uint32_t n, uint32_t flags, int32_t *dev_status_out,
+                          void *stream);
+
+/* The same gate on the host: the addresses in ops are HOST addresses, status
+ * a host array, and no GPU is needed.  Same refusals (nothing written), same
+ * packets and status bit for bit. */
+int lizec_read_gate_host(const lizec_read_op *ops, uint32_t n, uint32_t flags,
+                         int32_t *status);
+
 /* Pinned host memory for the streaming APIs (hipHostMalloc/hipHostFree):
  * pageable buffers work too but degrade the pipeline to synchronous
  * copies. */

@@ -12,6 +12,8 @@ package is the host-side mirror of the reference's EC surfaces:
                               another (goal change)
   lizardfs_amd.writegate    — the batched hdd_write gate: byte-range data
                               and block CRC checks, new block CRCs
+  lizardfs_amd.readgate     — the batched hdd_read gate: block CRC check and
+                              READ_DATA payloads (CRC + bytes) of byte ranges
 
 PyTorch supplies device memory and streams only; all byte-level compute is
 the HIP library.  There is NO CPU fallback on the product path: using the
@@ -23,6 +25,7 @@ from .lib import lib as load_lib  # noqa: F401
 from . import ec  # noqa: F401
 from . import crc  # noqa: F401
 from . import writegate  # noqa: F401
+from . import readgate  # noqa: F401
 
-__all__ = ["slice_traits", "ec", "crc", "writegate", "load_lib", "gpu_count",
-           "LizecError"]
+__all__ = ["slice_traits", "ec", "crc", "writegate", "readgate", "load_lib",
+           "gpu_count", "LizecError"]

@@ -63,6 +63,9 @@
  *
  * LDS holds the constants only (T0 and the advance matrices M_0..M_16,
  * enough for zero runs up to 2^17 - 1 bytes), as in the fold kernels.
+ *
+ * The walk can carry a copy of the range (COPY; the read gate, read_gate.h):
+ * what it loads it also stores, shifted by a fixed distance.
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -81,19 +84,72 @@ typedef unsigned int crc_u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(1))) crc_u32x4 *crc_gunits;
 typedef const __attribute__((address_space(1))) uint8_t *crc_gbytes;
 
+/* The copy a range pass can carry (the read gate, read_gate.h): the bytes
+ * of the range are stored at `dst + (their offset in the range)` as they
+ * are walked.  The source units are 16-byte aligned; what their copies are
+ * aligned to is wave-uniform and picks the store: 16 bytes, a 16-byte
+ * vector that promises 4-byte alignment only (as ec_kernel_strided.h
+ * does), or 16 single bytes.  kCrcCopyNone walks without storing. */
+enum : uint32_t { kCrcCopy16 = 0, kCrcCopy4 = 1, kCrcCopy1 = 2,
+                  kCrcCopyNone = 3 };
+typedef crc_u32x4 crc_u32x4_a4 __attribute__((aligned(4)));
+typedef __attribute__((address_space(1))) crc_u32x4 *crc_gunits_w;
+typedef __attribute__((address_space(1))) crc_u32x4_a4 *crc_gunits_w4;
+typedef __attribute__((address_space(1))) uint8_t *crc_gbytes_w;
+
+/* form = (dst - src) mod 16 of a copy, as a store form */
+__device__ __forceinline__ uint32_t crc_copy_form(uint64_t dst, uint64_t src) {
+	const uint32_t d = (uint32_t)(dst - src) & 15u;
+	return d == 0 ? kCrcCopy16 : (d & 3u) == 0 ? kCrcCopy4 : kCrcCopy1;
+}
+
+/* One byte, stored as one byte.  Plain neighbouring byte stores are merged
+ * by the compiler into dword and 16-byte stores at whatever address they
+ * have; a relaxed atomic of wavefront scope is the same global_store_byte,
+ * with no cache bits and no wait, and is left alone. */
+__device__ __forceinline__ void crc_store_byte(crc_gbytes_w p, uint32_t v) {
+	__hip_atomic_store(p, (uint8_t)v, __ATOMIC_RELAXED,
+	                   __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+
+/* Store one 16-byte unit at dst in the given form (not kCrcCopyNone). */
+__device__ __forceinline__ void crc_store_unit(uint64_t dst, uint32_t form,
+                                               crc_u32x4 w) {
+	if (form == kCrcCopy16) {
+		*(crc_gunits_w)dst = w;
+	} else if (form == kCrcCopy4) {
+		*(crc_gunits_w4)dst = w;
+	} else {
+		const crc_gbytes_w b = (crc_gbytes_w)dst;
+#pragma unroll
+		for (int k = 0; k < 16; ++k)
+			crc_store_byte(b + k, w[k >> 2] >> (8 * (k & 3)));
+	}
+}
+
 /* Fold units [i, i + N) of a lane's run into acc: N loads, then N folds.
  * The lane's incoming state `s` goes into the first word of unit 0; the
- * accumulator starts as zero there, and folding zero leaves the data. */
-template <int N, bool OR>
+ * accumulator starts as zero there, and folding zero leaves the data.
+ * With COPY the units are stored at dst + 16 * (i + q) as loaded. */
+template <int N, bool OR, bool COPY = false>
 __device__ __forceinline__ void crc_range_burst(uint32_t (&acc)[4],
                                                 crc_gunits u, uint32_t i,
-                                                uint32_t s, uint32_t &nz) {
+                                                uint32_t s, uint32_t &nz,
+                                                uint64_t dst = 0,
+                                                uint32_t form = kCrcCopyNone) {
 	crc_u32x4 w[N];
 #pragma unroll
 	for (int q = 0; q < N; ++q) w[q] = u[i + q];
 	if (OR) {
 #pragma unroll
 		for (int q = 0; q < N; ++q) nz |= w[q].x | w[q].y | w[q].z | w[q].w;
+	}
+	if (COPY) {
+		if (form != kCrcCopyNone) {
+#pragma unroll
+			for (int q = 0; q < N; ++q)
+				crc_store_unit(dst + ((uint64_t)(i + q) << 4), form, w[q]);
+		}
 	}
 	w[0].x ^= (i == 0 ? s : 0u);
 #pragma unroll
@@ -104,11 +160,14 @@ __device__ __forceinline__ void crc_range_burst(uint32_t (&acc)[4],
 
 /* Per-wave CRC of [p, p + len); p and len are wave-uniform.  Every lane
  * returns the CRC.  With OR, *any_nz tells whether any byte of the range is
- * non-zero. */
-template <bool OR>
+ * non-zero.  With COPY and a form other than kCrcCopyNone the range is also
+ * copied to [dst, dst + len): units by the lanes that fold them, head and
+ * tail bytes by lane 0; form must be crc_copy_form(dst, addr). */
+template <bool OR, bool COPY = false>
 __device__ uint32_t crc_range_wave(uint64_t addr, uint32_t len, uint32_t seed,
                                    const uint32_t *T0, const uint32_t *mats,
-                                   int lane, bool *any_nz) {
+                                   int lane, bool *any_nz, uint64_t dst = 0,
+                                   uint32_t form = kCrcCopyNone) {
 	const crc_gbytes p = (crc_gbytes)addr;
 	const uint32_t to16 = (0u - (uint32_t)addr) & 15u;
 	const uint32_t head = to16 < len ? to16 : len;
@@ -126,24 +185,30 @@ __device__ uint32_t crc_range_wave(uint64_t addr, uint32_t len, uint32_t seed,
 		for (uint32_t i = 0; i < head; ++i) {
 			uint32_t b = p[i];
 			if (OR) nz |= b;
+			if (COPY) {
+				if (form != kCrcCopyNone) ((crc_gbytes_w)dst)[i] = (uint8_t)b;
+			}
 			s = (s >> 8) ^ T0[(s ^ b) & 0xFFu];
 		}
 	}
 	if (cnt) {
 		/* 16-byte aligned: addr + head is, whenever units > 0 */
 		const crc_gunits u = (crc_gunits)(addr + head) + first;
+		/* where this lane's unit 0 goes */
+		const uint64_t d = dst + head + ((uint64_t)first << 4);
 		uint32_t acc[4] = {0u, 0u, 0u, 0u};
 		uint32_t i = 0;
-		for (; i + 8 <= cnt; i += 8) crc_range_burst<8, OR>(acc, u, i, s, nz);
+		for (; i + 8 <= cnt; i += 8)
+			crc_range_burst<8, OR, COPY>(acc, u, i, s, nz, d, form);
 		if (i + 4 <= cnt) {
-			crc_range_burst<4, OR>(acc, u, i, s, nz);
+			crc_range_burst<4, OR, COPY>(acc, u, i, s, nz, d, form);
 			i += 4;
 		}
 		if (i + 2 <= cnt) {
-			crc_range_burst<2, OR>(acc, u, i, s, nz);
+			crc_range_burst<2, OR, COPY>(acc, u, i, s, nz, d, form);
 			i += 2;
 		}
-		if (i < cnt) crc_range_burst<1, OR>(acc, u, i, s, nz);
+		if (i < cnt) crc_range_burst<1, OR, COPY>(acc, u, i, s, nz, d, form);
 		s = crc_reduce16(acc, T0);
 	}
 	/* raw states are linear in the message: advance each lane's by the
@@ -162,6 +227,10 @@ __device__ uint32_t crc_range_wave(uint64_t addr, uint32_t len, uint32_t seed,
 	for (uint32_t i = 0; i < tail; ++i) {
 		uint32_t b = t[i];
 		if (OR) nz |= b;
+		if (COPY) {
+			if (form != kCrcCopyNone && lane == 0)
+				((crc_gbytes_w)dst)[head + (units << 4) + i] = (uint8_t)b;
+		}
 		s = (s >> 8) ^ T0[(s ^ b) & 0xFFu];
 	}
 	if (OR) *any_nz = __ballot(nz != 0) != 0;

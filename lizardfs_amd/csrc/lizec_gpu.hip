@@ -45,6 +45,7 @@
 #include "ec_kernel_view.h"
 #include "crc_fold.h"
 #include "crc_ranges.h"
+#include "read_gate.h"
 
 /* Product kernel configuration (chosen by the variant A/B harness,
  * bench_variants.hip; numbers in profiles/ROUND1.md + ROUND2.md):
@@ -1723,6 +1724,51 @@ extern "C" int lizec_write_gate_batch(lizec_engine *e,
 	                   dim3(kCrcRangesThreads), 0, s, d_ops, n, flags, d_crcs,
 	                   d_nz, e->d_crc_const + kCrcTabWords, dev_status_out,
 	                   dev_newcrc_out);
+	LIZEC_CHECK(hipGetLastError());
+	return LIZEC_OK;
+}
+
+/* ------------------------------------------------------------------ */
+/* The read gate (read_gate.h)                                        */
+/* ------------------------------------------------------------------ */
+
+static_assert(sizeof(lizec_read_op) == 32, "lizec_read_op has padding");
+
+extern "C" int lizec_impl_read_gate_check(const lizec_read_op *ops, uint32_t n,
+                                          uint32_t flags);
+
+extern "C" int lizec_read_gate_batch(lizec_engine *e, const lizec_read_op *ops,
+                                     uint32_t n, uint32_t flags,
+                                     int32_t *dev_status_out, void *stream) {
+	if (!e || !dev_status_out) return LIZEC_EINVAL;
+	int r = lizec_impl_read_gate_check(ops, n, flags);
+	if (r != LIZEC_OK) return r;
+	hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+	LIZEC_CHECK(hipSetDevice(e->device));
+	/* scratch, in u64 slots: [ops 4n], uploaded; the kernel needs no other */
+	const size_t N = n;
+	lizec_stream_ctx *c;
+	r = ctx_acquire(e, s, 4 * N, N * sizeof(lizec_read_op), &c);
+	if (r != LIZEC_OK) return r;
+	uint8_t *st = c->h_staging + (size_t)kECTblBytes * 32 * 32;
+	memcpy(st, ops, N * sizeof(lizec_read_op));
+	LIZEC_CHECK(hipMemcpyAsync(c->d_ptrs, st, N * sizeof(lizec_read_op),
+	                           hipMemcpyHostToDevice, s));
+	LIZEC_CHECK(hipEventRecord(c->uploaded, s));
+	c->ev_recorded = true;
+	const lizec_read_op *d_ops = (const lizec_read_op *)c->d_ptrs;
+	uint32_t groups = (n + 3) / 4;
+	uint32_t grid = groups < kCrcRangesMaxGrid ? groups : kCrcRangesMaxGrid;
+	if (flags & LIZEC_GATE_SPARSE)
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(read_gate_kernel<true>), dim3(grid),
+		                   dim3(kCrcRangesThreads), 0, s, d_ops, n,
+		                   e->d_crc_const, e->d_crc_const + kCrcTabWords,
+		                   dev_status_out);
+	else
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(read_gate_kernel<false>),
+		                   dim3(grid), dim3(kCrcRangesThreads), 0, s, d_ops, n,
+		                   e->d_crc_const, e->d_crc_const + kCrcTabWords,
+		                   dev_status_out);
 	LIZEC_CHECK(hipGetLastError());
 	return LIZEC_OK;
 }

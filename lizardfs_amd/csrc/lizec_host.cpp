@@ -464,6 +464,65 @@ extern "C" int lizec_write_gate_host(const lizec_write_op *ops, uint32_t n,
 	return LIZEC_OK;
 }
 
+/* The host checks of the read gate, shared by lizec_read_gate_host and
+ * lizec_read_gate_batch (lizec_gpu.hip): hdd_read's own bounds
+ * (hddspacemgr.cc:1668-1671) plus what an address table can get wrong. */
+extern "C" int lizec_impl_read_gate_check(const lizec_read_op *ops, uint32_t n,
+                                          uint32_t flags) {
+	if (!ops || n == 0 || n > (1u << 24)) return LIZEC_EINVAL;
+	if (flags & ~(uint32_t)LIZEC_GATE_SPARSE) return LIZEC_EINVAL;
+	for (uint32_t i = 0; i < n; ++i) {
+		const lizec_read_op &op = ops[i];
+		if (op.size == 0 || op.size > 65536u || op.offset >= 65536u ||
+		    op.offset + op.size > 65536u)
+			return LIZEC_EINVAL;
+		if (op.out == 0) return LIZEC_EINVAL;
+		if (op.block != 0 && op.stored == 0) return LIZEC_EINVAL;
+	}
+	return LIZEC_OK;
+}
+
+/* hdd_read over hdd_read_crc_and_block (hddspacemgr.cc:1525-1608,
+ * :1709-1722) over host memory; see lizec.h. */
+extern "C" int lizec_read_gate_host(const lizec_read_op *ops, uint32_t n,
+                                    uint32_t flags, int32_t *status) {
+	if (!status) return LIZEC_EINVAL;
+	int r = lizec_impl_read_gate_check(ops, n, flags);
+	if (r != LIZEC_OK) return r;
+	for (uint32_t i = 0; i < n; ++i) {
+		const lizec_read_op &op = ops[i];
+		uint8_t *out = (uint8_t *)(uintptr_t)op.out;
+		uint32_t crc;
+		status[i] = LIZEC_GATE_OK;
+		if (op.block == 0) {                                   /* :1535 */
+			crc = lizec_crc32_zeroblock(0, op.size);
+			memset(out + 4, 0, op.size);
+		} else {
+			const uint8_t *b = (const uint8_t *)(uintptr_t)op.block;
+			const uint8_t *p = (const uint8_t *)(uintptr_t)op.stored;
+			const uint32_t end = op.offset + op.size;
+			const uint32_t mid = lizec_crc32(0, b + op.offset, op.size);
+			const uint32_t have = lizec_crc32_splice(
+			    lizec_crc32(0, b, op.offset), op.offset, mid, op.size,
+			    lizec_crc32(0, b + end, 65536u - end), 65536u);
+			uint32_t blk = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) |
+			               ((uint32_t)p[2] << 8) | p[3];
+			if ((flags & LIZEC_GATE_SPARSE) && blk == 0)       /* :1571 */
+				lizec_recompute_crc_if_block_empty(b, 65536u, &blk);
+			else if (blk != have)                              /* :1552 */
+				status[i] = LIZEC_GATE_BAD_BLOCK;
+			crc = (op.offset == 0 && op.size == 65536u) ? blk : mid;
+			if (status[i] != LIZEC_GATE_OK) crc = 0;
+			memcpy(out + 4, b + op.offset, op.size);
+		}
+		out[0] = (uint8_t)(crc >> 24);
+		out[1] = (uint8_t)(crc >> 16);
+		out[2] = (uint8_t)(crc >> 8);
+		out[3] = (uint8_t)crc;
+	}
+	return LIZEC_OK;
+}
+
 /* C++-linkage aliases so a LizardFS build linking against common/crc.h's
  * mangled symbols (crc.h:25-31) resolves them from this library. */
 uint32_t mycrc32(uint32_t crc, const uint8_t *block, uint32_t leng) {

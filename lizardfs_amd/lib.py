@@ -162,6 +162,13 @@ def lib():
     L.lizec_write_gate_host.argtypes = [
         ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
         ctypes.c_void_p]
+    L.lizec_read_gate_batch.restype = ctypes.c_int
+    L.lizec_read_gate_batch.argtypes = [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+        ctypes.c_void_p, ctypes.c_void_p]
+    L.lizec_read_gate_host.restype = ctypes.c_int
+    L.lizec_read_gate_host.argtypes = [
+        ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
     _lib = L
     return _lib
 
