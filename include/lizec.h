@@ -610,7 +610,20 @@ void lizec_host_free(void *p);
  *  sigs        : nchunks*oc signatures (sig_len bytes each), or NULL
  *  header_size : image header bytes; crc_off: CRC array offset within it
  *  host_dst    : nchunks*oc HOST addresses, header_size+part_len each
- *  sub_batch   : chunks per pipeline stage (0 = auto, ~1 GiB staging) */
+ *  sub_batch   : chunks per pipeline stage (0 = auto, ~1 GiB staging;
+ *                clamped to nchunks)
+ * Returns LIZEC_EINVAL from the host, with nothing allocated or enqueued
+ * and no byte of the destinations written, for a NULL e, gftbls, host_src
+ * or host_dst, nchunks < 1, ic or oc outside 1..32, part_len 0, not a
+ * multiple of 65536 or above 2^31, sig_len > header_size, a CRC array that
+ * does not fit in the header (crc_off + 4*(part_len/65536) > header_size),
+ * or a header_size that is not a multiple of 16: the images are staged
+ * back to back and their blocks, header_size in, are read and written with
+ * 16-byte vector accesses (every real header is a multiple of 1024,
+ * chunk.cc getHeaderSize).  sigs == NULL or sig_len == 0 leaves the
+ * signature block zero.  Exactly header_size + part_len bytes are written
+ * at every destination address and part_len read at every source address;
+ * the addresses are otherwise unrelated (any row stride on either side). */
 int lizec_replicate_run(lizec_engine *e, uint64_t part_len, int ic, int oc,
                         const uint8_t *gftbls, const uint64_t *host_src,
                         const uint8_t *sigs, uint32_t sig_len,

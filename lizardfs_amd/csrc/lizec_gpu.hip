@@ -2160,6 +2160,11 @@ extern "C" int lizec_replicate_run(lizec_engine *e, uint64_t part_len,
 	if (r != LIZEC_OK) return r;
 	if (sig_len > header_size || crc_off + 4 * (part_len / 65536) > header_size)
 		return LIZEC_EINVAL;
+	/* the staged images are packed at n*(header_size + part_len) and their
+	 * blocks start header_size in: run_batch reads and writes them with
+	 * 16-byte vector accesses and checks no alignment of its own
+	 * (check_part_addrs is the public call's) */
+	if (header_size % 16) return LIZEC_EINVAL;
 	const repl_layout lay = {header_size + part_len, header_size, header_size,
 	                         crc_off, kECBlockBytes, 4u};
 	return replicate_run_impl(e, part_len, ic, oc, gftbls, host_src, sigs,

@@ -247,6 +247,18 @@ def convert_part_images(src_slice, fragments, chunk_blocks, target_slice,
     return images
 
 
+def _check_rows(a, what):
+    """The C side is handed one address per row (base + s*strides[0]) and
+    takes a row's bytes to be contiguous there: rows may lie any distance
+    apart, but not backwards (the address arithmetic is unsigned), and a
+    row's bytes must be adjacent."""
+    if a.strides[1] != 1:
+        raise ValueError(f"{what}: rows must be contiguous "
+                         f"(inner stride {a.strides[1]}, not 1)")
+    if a.strides[0] < 0:
+        raise ValueError(f"{what}: negative row stride {a.strides[0]}")
+
+
 def replicate_stream(k, m, host_parts, erased, want, chunk_ids, version,
                      out=None, device=0, sub_batch=0, fmt="moosefs"):
     """The full ChunkReplicator::replicate pipeline
@@ -256,7 +268,10 @@ def replicate_stream(k, m, host_parts, erased, want, chunk_ids, version,
 
     host_parts: list of k+m entries; entry i is a numpy uint8 [S, L] array
       (surviving part bytes, L a multiple of 64 KiB) or None (erased).
-      Use lib.pinned_empty for true copy/compute overlap.
+      Use lib.pinned_empty for true copy/compute overlap.  Rows may lie any
+      distance apart (a row-strided view is fine), but each row's bytes
+      must be contiguous and the row stride not negative; the same holds
+      for the arrays of `out`.  Anything else raises ValueError.
     erased: exactly m part indices; want: subset to rebuild.
     out: optional dict part -> uint8 [S, hdr+L] array to fill (pinned
       recommended); allocated (pinned) if absent.
@@ -292,6 +307,7 @@ def replicate_stream(k, m, host_parts, erased, want, chunk_ids, version,
             S, plen = a.shape
         elif a.shape != (S, plen):
             raise ValueError("part shapes differ")
+        _check_rows(a, f"part {i}")
     if plen % st.BLOCK_SIZE:
         raise ValueError("part length must be whole 64 KiB blocks")
     if len(chunk_ids) != S:
@@ -299,6 +315,21 @@ def replicate_stream(k, m, host_parts, erased, want, chunk_ids, version,
 
     slice_type = st.ec_slice_type(k, m)
     hdr = scrub.header_size(slice_type)
+    img_bytes = hdr + plen
+    if fmt == "interleaved":
+        img_bytes = plen // st.BLOCK_SIZE * scrub.HDD_BLOCK
+    if out is not None:
+        for p in want:
+            if p not in out:
+                raise ValueError(f"out has no array for wanted part {p}")
+            a = out[p]
+            if a.dtype != np.uint8 or a.shape != (S, img_bytes):
+                raise ValueError(
+                    f"out[{p}] must be uint8 [S={S}, {img_bytes}]")
+            _check_rows(a, f"out[{p}]")
+            if S > 1 and a.strides[0] < img_bytes:
+                raise ValueError(f"out[{p}]: rows overlap (row stride "
+                                 f"{a.strides[0]} < {img_bytes})")
     present = sum(1 << i for i in surv)
     needed = sum(1 << i for i in want)
     lib = L.lib()
@@ -312,14 +343,8 @@ def replicate_stream(k, m, host_parts, erased, want, chunk_ids, version,
     ic, oc = ic.value, oc.value
     assert (ic, oc) == (len(surv), len(want))
 
-    img_bytes = hdr + plen
-    if fmt == "interleaved":
-        img_bytes = plen // st.BLOCK_SIZE * scrub.HDD_BLOCK
     if out is None:
         out = {p: L.pinned_empty((S, img_bytes)) for p in want}
-    for p in want:
-        if out[p].dtype != np.uint8 or out[p].shape != (S, img_bytes):
-            raise ValueError(f"out[{p}] must be uint8 [S={S}, {img_bytes}]")
 
     src = np.empty((S, ic), np.uint64)
     for j, i in enumerate(surv):
