@@ -359,6 +359,100 @@ int64_t lizec_ragged_block_map(const uint32_t *dst_nblocks, int dests,
                                int num_stripes, uint32_t *map,
                                uint64_t cap_entries);
 
+/* Batched chunk READ — ChunkReader::readData (chunk_reader.cc:85-131) for
+ * num_reads requests at once: chunk blocks [first_block, first_block +
+ * block_count) gathered from the parts of one slice, whose data parts
+ * interleave the chunk round-robin (ChunkReadPlanner,
+ * chunk_read_planner.h:86-162), the blocks of lost parts rebuilt on the way
+ * (ECReadPlan::recoverParts, ec_read_plan.h:113-146;
+ * XorReadPlan::postProcessRead, xor_read_plan.h:77-126) and everything put
+ * into chunk order (BlockConverter, chunk_read_planner.h:36-58).  One read
+ * is one readData request on one chunk.
+ *  srcs       : source slots per read, 1..32
+ *  rows       : rows of a coefficient table, 0..32: the most columns that a
+ *             read of the call rebuilds.  0 makes the call a pure gather —
+ *             BlockConverter on the device for a healthy slice; gftbls,
+ *             ntables and tbl_index are then ignored and may be NULL / 0.
+ *  gftbls, ntables, tbl_index: as for lizec_ec_encode_batch_ragged, tables
+ *             of 32*srcs*rows bytes; a read that rebuilds fewer than `rows`
+ *             columns leaves the other rows unreferenced
+ *  src_dptrs / src_nblocks: HOST arrays [num_reads][srcs]: the parts of the
+ *             slice that the read uses, by the ragged call's rules — address
+ *             of block 0's data and block count; source j has block b iff
+ *             b < its count, beyond that it counts as zeros and no byte of
+ *             it is read; a slot of count 0 may have address 0.  The counts
+ *             of a short chunk's parts (slice_traits.h:311-316) are how the
+ *             chunk's end is expressed: there is no chunk length.
+ *  view_parts : ks, the data parts of the slice, 1..32; one value per call.
+ *             Chunk block c is row c / ks, column c % ks.
+ *  col_map    : HOST array [num_reads][ks], where a column comes from:
+ *             j < srcs   = source slot j, copied;
+ *             0x80 + r, r < rows = lost, and equal to table row r applied to
+ *                          the read's sources (XOR_j tbl[r][j] * src_j[row],
+ *                          absent sources skipped);
+ *             0xFF       = unmapped, legal only if no requested block of the
+ *                          read falls in the column.
+ *             No slot and no row may stand for two columns of one read.
+ *  first_block / block_count / dst_dptrs: HOST arrays [num_reads]: output
+ *             block i < block_count is chunk block first_block + i, 65536
+ *             bytes at dst + i*dst_block_stride.  A range may start and end
+ *             anywhere inside a row.  A requested block that none of its
+ *             sources reaches (at or past the chunk's end) is written as
+ *             zeros, as SliceReadPlan::postProcessRead pads
+ *             (slice_read_plan.h:94-105).
+ *  src_block_stride / dst_block_stride: as for the strided call; a
+ *             dst_block_stride above 65536 leaves the bytes between two
+ *             output blocks (the CRC slots of an INTERLEAVED image) alone
+ * Only the counted source blocks are read — and of those only the ones a
+ * row needs: a row without a lost requested column reads just its requested
+ * columns.  Only the requested output blocks are written.  An output must
+ * not overlap any source or other output of the call.
+ * One launch per pass of 8 table rows (one launch at rows == 0); one
+ * workgroup per tile of every (read, block row) that a range touches loads
+ * each source tile once, stores it to the output block of the column it
+ * backs and accumulates it into the lost columns' rows
+ * (csrc/ec_kernel_read.h).  Copies happen in the first pass only.
+ * Scratch cost, device and pinned host each: per read 20 bytes, 16 bytes per
+ * source slot and 4 per table row, plus 8 bytes per (read, block row); per
+ * call the tables (32*srcs*rows*ntables bytes) and up to 15 bytes of padding
+ * behind each of seven sections.  A whole-chunk ec(8,2) read (128 block
+ * rows) takes about 1.2 KiB.  Kept with the stream's scratch as for the
+ * gates.
+ * Returns LIZEC_EINVAL from the host, with nothing enqueued and no output
+ * byte written, for everything the ragged call refuses about sources, tables
+ * (at rows > 0) and strides; view_parts or srcs outside 1..32, rows outside
+ * 0..32; a col_map value that names a slot >= srcs or a row >= rows, or a
+ * slot or row named twice; a requested column that is unmapped, or mapped to
+ * a slot of address 0; block_count == 0 or first_block + block_count >
+ * 1048576; a destination address that is 0 or not a multiple of 4; a NULL
+ * array; num_reads < 1; or (read, block row) pairs times 8 above 2^31-1.
+ * A side whose stride and used addresses are all multiples of 16 keeps the
+ * aligned vector accesses.  There is no plan form.  Stream and thread
+ * contract as for the other batch calls. */
+int lizec_chunk_read_batch(lizec_engine *e, int srcs, int rows,
+                           const uint8_t *gftbls, int ntables,
+                           const uint32_t *tbl_index,
+                           const uint64_t *src_dptrs,
+                           const uint32_t *src_nblocks, int view_parts,
+                           const uint8_t *col_map, const uint32_t *first_block,
+                           const uint32_t *block_count,
+                           const uint64_t *dst_dptrs, int num_reads,
+                           uint32_t src_block_stride,
+                           uint32_t dst_block_stride, void *stream);
+
+/* The same read on the host: the addresses are HOST addresses and no GPU is
+ * needed (memcpy for the copied columns, ec_encode_data over the present
+ * sources for the lost ones).  Same refusals (nothing written), same bytes. */
+int lizec_chunk_read_host(int srcs, int rows, const uint8_t *gftbls,
+                          int ntables, const uint32_t *tbl_index,
+                          const uint64_t *src_ptrs,
+                          const uint32_t *src_nblocks, int view_parts,
+                          const uint8_t *col_map, const uint32_t *first_block,
+                          const uint32_t *block_count,
+                          const uint64_t *dst_ptrs, int num_reads,
+                          uint32_t src_block_stride,
+                          uint32_t dst_block_stride);
+
 /* Per-block CRC32 over a contiguous device buffer:
  *  dev_crcs_out[b] = lizec_crc32(seed, dev_buf + b*block_len, block_len)
  * The chunkserver's per-64KiB-block gate (hddspacemgr.cc:1918-1920, scrub

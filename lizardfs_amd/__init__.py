@@ -10,6 +10,9 @@ package is the host-side mirror of the reference's EC surfaces:
   lizardfs_amd.crc          — per-block CRC32 (GPU batch + host scalar)
   lizardfs_amd.convert      — parts of one slice type from a chunk held in
                               another (goal change)
+  lizardfs_amd.chunkread    — the client read: block ranges of chunks
+                              gathered from a slice's parts, lost parts
+                              rebuilt on the way
   lizardfs_amd.writegate    — the batched hdd_write gate: byte-range data
                               and block CRC checks, new block CRCs
   lizardfs_amd.readgate     — the batched hdd_read gate: block CRC check and

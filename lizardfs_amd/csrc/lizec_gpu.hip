@@ -43,6 +43,7 @@
 #include "ec_kernel_strided.h"
 #include "ec_kernel_ragged.h"
 #include "ec_kernel_view.h"
+#include "ec_kernel_read.h"
 #include "crc_fold.h"
 #include "crc_ranges.h"
 #include "read_gate.h"
@@ -1187,6 +1188,165 @@ extern "C" int lizec_ec_encode_batch_view(
 		default: LIZEC_LAUNCH_VIEW_D(8); break;
 		}
 #undef LIZEC_LAUNCH_VIEW_D
+		base += d;
+	}
+	LIZEC_CHECK(hipGetLastError());
+	return LIZEC_OK;
+}
+
+/* ------------------------------------------------------------------ */
+/* Chunk reads: block ranges gathered from the parts of a slice, lost  */
+/* parts rebuilt on the way (ec_kernel_read.h)                         */
+/* ------------------------------------------------------------------ */
+
+struct read_dev {
+	const uint8_t *tbls;
+	const uint32_t *index;
+	const uint2 *map;
+	const uint64_t *src, *dst;
+	const uint32_t *src_nb, *slot_col, *row_col;
+	const uint2 *range;
+	uint32_t view_parts;
+};
+
+/* One pass of the read kernel: the grid of launch_ec_ragged.  D = 0 is the
+ * pure gather and needs no LDS. */
+template <int D>
+static void launch_chunk_read(uint32_t entries, int srcs, int dest_base,
+                              int rows, const read_dev &r, uint32_t src_stride,
+                              uint32_t dst_stride, bool sal, bool dal,
+                              hipStream_t s) {
+	constexpr int CH = ec_chunks_for(D);
+	uint32_t total_tiles = entries * (kECBlockBytes / (kChunkBytes * CH));
+	size_t lds = (size_t)D * srcs * kECTblBytes;
+#define LIZEC_LAUNCH_READ(SAL, DAL)                                         \
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(ec_chunk_read_kernel<D, CH, SAL, DAL>), \
+	                   dim3(total_tiles), dim3(kThreads), lds, s, srcs,     \
+	                   dest_base, rows, r.tbls, r.index, r.map, r.src,      \
+	                   r.src_nb, r.slot_col, r.row_col, r.view_parts,       \
+	                   r.range, r.dst, src_stride, dst_stride)
+	if (sal && dal) LIZEC_LAUNCH_READ(true, true);
+	else if (sal) LIZEC_LAUNCH_READ(true, false);
+	else if (dal) LIZEC_LAUNCH_READ(false, true);
+	else LIZEC_LAUNCH_READ(false, false);
+#undef LIZEC_LAUNCH_READ
+}
+
+extern "C" int64_t lizec_impl_chunk_read_check(
+    int srcs, int rows, const uint8_t *gftbls, int ntables,
+    const uint32_t *tbl_index, const uint64_t *src_dptrs,
+    const uint32_t *src_nblocks, int view_parts, const uint8_t *col_map,
+    const uint32_t *first_block, const uint32_t *block_count,
+    const uint64_t *dst_dptrs, int num_reads, uint32_t src_block_stride,
+    uint32_t dst_block_stride, uint64_t *sbits_out, uint64_t *dbits_out);
+
+extern "C" int lizec_chunk_read_batch(
+    lizec_engine *e, int srcs, int rows, const uint8_t *gftbls, int ntables,
+    const uint32_t *tbl_index, const uint64_t *src_dptrs,
+    const uint32_t *src_nblocks, int view_parts, const uint8_t *col_map,
+    const uint32_t *first_block, const uint32_t *block_count,
+    const uint64_t *dst_dptrs, int num_reads, uint32_t src_block_stride,
+    uint32_t dst_block_stride, void *stream) {
+	if (!e) return LIZEC_EINVAL;
+	uint64_t sbits, dbits;
+	int64_t entries = lizec_impl_chunk_read_check(
+	    srcs, rows, gftbls, ntables, tbl_index, src_dptrs, src_nblocks,
+	    view_parts, col_map, first_block, block_count, dst_dptrs, num_reads,
+	    src_block_stride, dst_block_stride, &sbits, &dbits);
+	if (entries <= 0) return LIZEC_EINVAL;
+	const bool sal = (sbits & 15) == 0, dal = (dbits & 15) == 0;
+	hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+	LIZEC_CHECK(hipSetDevice(e->device));
+
+	/* the ragged call's scratch with the read's own tables in place of the
+	 * destination counts; every section 16-byte aligned */
+	auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+	const size_t R = (size_t)num_reads, ks = (size_t)view_parts;
+	const size_t nsrc = R * srcs, nrow = R * rows;
+	size_t ntbl = rows ? (size_t)ntables * srcs * rows : 0;   /* 32 B each */
+	size_t o_index = up16(ntbl * kECTblBytes);
+	size_t o_map = o_index + up16(R * 4);
+	size_t o_snb = o_map + up16((size_t)entries * 8);
+	size_t o_scol = o_snb + up16(nsrc * 4);
+	size_t o_rcol = o_scol + up16(nsrc * 4);
+	size_t o_range = o_rcol + up16(nrow * 4);
+	size_t bytes = o_range + up16(R * 8);
+	lizec_stream_ctx *c;
+	int r = ctx_acquire_ragged(e, s, nsrc + R, (nsrc + R) * 8, bytes, &c);
+	if (r != LIZEC_OK) return r;
+	uint8_t *h = c->h_ragged;
+	for (size_t i = 0; i < ntbl; ++i)
+		pack_mixed_radix(gftbls + i * 32, h + i * kECTblBytes);
+	if (rows && tbl_index)
+		memcpy(h + o_index, tbl_index, R * 4);
+	else
+		memset(h + o_index, 0, R * 4);
+	/* the row map, and the two inverses of col_map: the column a slot backs
+	 * and the column a table row stands for */
+	uint32_t *map = (uint32_t *)(h + o_map);
+	uint32_t *scol = (uint32_t *)(h + o_scol);
+	uint32_t *rcol = (uint32_t *)(h + o_rcol);
+	uint32_t *range = (uint32_t *)(h + o_range);
+	memset(scol, 0xFF, nsrc * 4);
+	memset(rcol, 0xFF, nrow * 4);
+	for (size_t i = 0; i < R; ++i) {
+		const uint32_t first = first_block[i];
+		const uint32_t last = first + block_count[i] - 1;
+		for (uint32_t b = first / (uint32_t)ks; b <= last / (uint32_t)ks; ++b) {
+			*map++ = (uint32_t)i;
+			*map++ = b;
+		}
+		for (size_t col = 0; col < ks; ++col) {
+			const uint8_t v = col_map[i * ks + col];
+			if (v == 0xFF) continue;
+			if (v >= 0x80) rcol[i * rows + (v - 0x80)] = (uint32_t)col;
+			else scol[i * srcs + v] = (uint32_t)col;
+		}
+		range[2 * i] = first;
+		range[2 * i + 1] = block_count[i];
+	}
+	memcpy(h + o_snb, src_nblocks, nsrc * 4);
+	uint64_t *pstage = (uint64_t *)(c->h_staging + (size_t)kECTblBytes * 32 * 32);
+	memcpy(pstage, src_dptrs, nsrc * 8);
+	memcpy(pstage + nsrc, dst_dptrs, R * 8);
+	LIZEC_CHECK(hipMemcpyAsync(c->d_ragged, h, bytes, hipMemcpyHostToDevice, s));
+	LIZEC_CHECK(hipMemcpyAsync(c->d_ptrs, pstage, (nsrc + R) * 8,
+	                           hipMemcpyHostToDevice, s));
+	LIZEC_CHECK(hipEventRecord(c->uploaded, s));
+	c->ev_recorded = true;
+
+	read_dev rd;
+	rd.tbls = c->d_ragged;
+	rd.index = (const uint32_t *)(c->d_ragged + o_index);
+	rd.map = (const uint2 *)(c->d_ragged + o_map);
+	rd.src_nb = (const uint32_t *)(c->d_ragged + o_snb);
+	rd.slot_col = (const uint32_t *)(c->d_ragged + o_scol);
+	rd.row_col = (const uint32_t *)(c->d_ragged + o_rcol);
+	rd.range = (const uint2 *)(c->d_ragged + o_range);
+	rd.src = c->d_ptrs;
+	rd.dst = c->d_ptrs + nsrc;
+	rd.view_parts = (uint32_t)view_parts;
+	/* passes of at most 8 table rows, as run_batch_strided; pass 0 copies */
+	if (rows == 0)
+		launch_chunk_read<0>((uint32_t)entries, srcs, 0, 0, rd,
+		                     src_block_stride, dst_block_stride, sal, dal, s);
+	for (int base = 0; base < rows;) {
+		int d = rows - base;
+		if (d > 8) d = 8;
+#define LIZEC_LAUNCH_READ_D(D)                                             \
+	launch_chunk_read<D>((uint32_t)entries, srcs, base, rows, rd,          \
+	                     src_block_stride, dst_block_stride, sal, dal, s)
+		switch (d) {
+		case 1: LIZEC_LAUNCH_READ_D(1); break;
+		case 2: LIZEC_LAUNCH_READ_D(2); break;
+		case 3: LIZEC_LAUNCH_READ_D(3); break;
+		case 4: LIZEC_LAUNCH_READ_D(4); break;
+		case 5: LIZEC_LAUNCH_READ_D(5); break;
+		case 6: LIZEC_LAUNCH_READ_D(6); break;
+		case 7: LIZEC_LAUNCH_READ_D(7); break;
+		default: LIZEC_LAUNCH_READ_D(8); break;
+		}
+#undef LIZEC_LAUNCH_READ_D
 		base += d;
 	}
 	LIZEC_CHECK(hipGetLastError());

@@ -652,3 +652,155 @@ extern "C" int64_t lizec_ragged_block_map(const uint32_t *dst_nblocks,
 	}
 	return (int64_t)entries;
 }
+
+/* ------------------------------------------------------------------ */
+/* Batched chunk read: the checks and the host twin (pure host)       */
+/* ------------------------------------------------------------------ */
+
+/* The host checks of the chunk read, shared by lizec_chunk_read_host and
+ * lizec_chunk_read_batch (lizec_gpu.hip).  Returns the entries of the row
+ * map (one per (read, block row) that a range touches) or LIZEC_EINVAL;
+ * *sbits / *dbits receive the OR of each side's stride and used addresses,
+ * whose low bits choose the kernel form. */
+extern "C" int64_t lizec_impl_chunk_read_check(
+    int srcs, int rows, const uint8_t *gftbls, int ntables,
+    const uint32_t *tbl_index, const uint64_t *src_dptrs,
+    const uint32_t *src_nblocks, int view_parts, const uint8_t *col_map,
+    const uint32_t *first_block, const uint32_t *block_count,
+    const uint64_t *dst_dptrs, int num_reads, uint32_t src_block_stride,
+    uint32_t dst_block_stride, uint64_t *sbits_out, uint64_t *dbits_out) {
+	if (!src_dptrs || !src_nblocks || !col_map || !first_block ||
+	    !block_count || !dst_dptrs)
+		return LIZEC_EINVAL;
+	if (srcs < 1 || srcs > 32 || rows < 0 || rows > 32 || view_parts < 1 ||
+	    view_parts > 32 || num_reads < 1)
+		return LIZEC_EINVAL;
+	if (rows > 0) {
+		if (!gftbls || ntables < 1 ||
+		    (uint64_t)ntables * 32 * srcs * rows > (uint64_t)1 << 30)
+			return LIZEC_EINVAL;
+		if (tbl_index)
+			for (int i = 0; i < num_reads; ++i)
+				if (tbl_index[i] >= (uint32_t)ntables) return LIZEC_EINVAL;
+	}
+	if (src_block_stride < 65536u || dst_block_stride < 65536u)
+		return LIZEC_EINVAL;
+	const uint32_t ks = (uint32_t)view_parts;
+	uint64_t sbits = src_block_stride, dbits = dst_block_stride;
+	uint64_t entries = 0;
+	for (int i = 0; i < num_reads; ++i) {
+		const uint64_t *sp = src_dptrs + (size_t)i * srcs;
+		const uint32_t *sn = src_nblocks + (size_t)i * srcs;
+		const uint8_t *cm = col_map + (size_t)i * ks;
+		/* the sources, by the ragged call's rules */
+		for (int j = 0; j < srcs; ++j) {
+			if (sn[j] > 32768u) return LIZEC_EINVAL;
+			if (!sn[j]) continue;
+			if (!sp[j]) return LIZEC_EINVAL;
+			sbits |= sp[j];
+		}
+		const uint64_t first = first_block[i], count = block_count[i];
+		if (count == 0 || first + count > 1048576u) return LIZEC_EINVAL;
+		if (!dst_dptrs[i]) return LIZEC_EINVAL;
+		dbits |= dst_dptrs[i];
+		/* the column map: every value names something that exists, and no
+		 * slot or table row stands for two columns */
+		uint32_t slots_seen = 0, rows_seen = 0;
+		for (uint32_t c = 0; c < ks; ++c) {
+			const uint32_t v = cm[c];
+			const bool req = count >= ks || (c + ks - first % ks) % ks < count;
+			if (v == 0xFF) {
+				if (req) return LIZEC_EINVAL;
+			} else if (v >= 0x80) {
+				const uint32_t r = v - 0x80;
+				if (r >= (uint32_t)rows || ((rows_seen >> r) & 1))
+					return LIZEC_EINVAL;
+				rows_seen |= 1u << r;
+			} else {
+				if (v >= (uint32_t)srcs || ((slots_seen >> v) & 1))
+					return LIZEC_EINVAL;
+				slots_seen |= 1u << v;
+				if (req && !sp[v]) return LIZEC_EINVAL;
+			}
+		}
+		entries += (first + count - 1) / ks - first / ks + 1;
+	}
+	if ((sbits | dbits) & 3) return LIZEC_EINVAL;
+	/* one workgroup per 8 KiB tile at the most, in a 31-bit grid */
+	if (entries * 8 > 0x7FFFFFFFull) return LIZEC_EINVAL;
+	if (sbits_out) *sbits_out = sbits;
+	if (dbits_out) *dbits_out = dbits;
+	return (int64_t)entries;
+}
+
+/* ChunkReader::readData over host memory, row by row: memcpy for the
+ * columns a source backs, ec_encode_data over the present sources for the
+ * lost ones; see lizec.h. */
+extern "C" int lizec_chunk_read_host(
+    int srcs, int rows, const uint8_t *gftbls, int ntables,
+    const uint32_t *tbl_index, const uint64_t *src_ptrs,
+    const uint32_t *src_nblocks, int view_parts, const uint8_t *col_map,
+    const uint32_t *first_block, const uint32_t *block_count,
+    const uint64_t *dst_ptrs, int num_reads, uint32_t src_block_stride,
+    uint32_t dst_block_stride) {
+	int64_t entries = lizec_impl_chunk_read_check(
+	    srcs, rows, gftbls, ntables, tbl_index, src_ptrs, src_nblocks,
+	    view_parts, col_map, first_block, block_count, dst_ptrs, num_reads,
+	    src_block_stride, dst_block_stride, nullptr, nullptr);
+	if (entries < 0) return (int)entries;
+	const uint32_t ks = (uint32_t)view_parts;
+	uint8_t tbl[32 * 32 * 32];   /* the lost rows over the present sources */
+	for (int i = 0; i < num_reads; ++i) {
+		const uint64_t *sp = src_ptrs + (size_t)i * srcs;
+		const uint32_t *sn = src_nblocks + (size_t)i * srcs;
+		const uint8_t *cm = col_map + (size_t)i * ks;
+		const uint8_t *rt =
+		    rows ? gftbls + (size_t)(tbl_index ? tbl_index[i] : 0) * 32 *
+		                        srcs * rows
+		         : nullptr;
+		uint8_t *dst = (uint8_t *)(uintptr_t)dst_ptrs[i];
+		const uint32_t first = first_block[i], end = first + block_count[i];
+		for (uint32_t b = first / ks; b <= (end - 1) / ks; ++b) {
+			const uint32_t c0 = b * ks;
+			const uint32_t lo = first > c0 ? first - c0 : 0;
+			const uint32_t hi = end - c0 < ks ? end - c0 : ks;
+			uint8_t *lost[32];
+			int lost_row[32], nl = 0;
+			for (uint32_t c = lo; c < hi; ++c) {
+				uint8_t *o = dst + (uint64_t)(c0 + c - first) * dst_block_stride;
+				const uint32_t v = cm[c];
+				if (v >= 0x80) {
+					lost[nl] = o;
+					lost_row[nl++] = (int)(v - 0x80);
+				} else if (b < sn[v]) {
+					memcpy(o, (const uint8_t *)(uintptr_t)sp[v] +
+					              (uint64_t)b * src_block_stride, 65536);
+				} else {
+					memset(o, 0, 65536);
+				}
+			}
+			if (!nl) continue;
+			uint8_t *in[32];
+			int np = 0;
+			for (int j = 0; j < srcs; ++j) {
+				if (b >= sn[j]) continue;
+				for (int l = 0; l < nl; ++l)
+					memcpy(tbl + ((size_t)l * srcs + np) * 32,
+					       rt + ((size_t)lost_row[l] * srcs + j) * 32, 32);
+				in[np++] = (uint8_t *)(uintptr_t)sp[j] +
+				           (uint64_t)b * src_block_stride;
+			}
+			if (!np) {
+				for (int l = 0; l < nl; ++l) memset(lost[l], 0, 65536);
+				continue;
+			}
+			/* the table was filled at row pitch srcs; close it up to np */
+			if (np < srcs)
+				for (int l = 1; l < nl; ++l)
+					memmove(tbl + (size_t)l * np * 32,
+					        tbl + (size_t)l * srcs * 32, (size_t)np * 32);
+			ec_encode_data(65536, np, nl, tbl, in, lost);
+		}
+	}
+	return LIZEC_OK;
+}

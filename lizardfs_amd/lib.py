@@ -169,6 +169,15 @@ def lib():
     L.lizec_read_gate_host.restype = ctypes.c_int
     L.lizec_read_gate_host.argtypes = [
         ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
+    read_args = [
+        ctypes.c_int, ctypes.c_int, u8p, ctypes.c_int, u32p, u64p, u32p,
+        ctypes.c_int, u8p, u32p, u32p, u64p, ctypes.c_int, ctypes.c_uint32,
+        ctypes.c_uint32]
+    L.lizec_chunk_read_batch.restype = ctypes.c_int
+    L.lizec_chunk_read_batch.argtypes = [ctypes.c_void_p] + read_args + \
+        [ctypes.c_void_p]
+    L.lizec_chunk_read_host.restype = ctypes.c_int
+    L.lizec_chunk_read_host.argtypes = read_args
     _lib = L
     return _lib
 
