@@ -453,6 +453,91 @@ int lizec_chunk_read_host(int srcs, int rows, const uint8_t *gftbls,
                           uint32_t src_block_stride,
                           uint32_t dst_block_stride);
 
+/* The CLIENT WRITE of an EC or xor slice: ChunkWriter::startOperation
+ * (mount/chunk_writer.cc:475-547) with computeParityBlock (:365-402) and the
+ * CRCs of WriteExecutor::addDataPacket (write_executor.cc:91-107), for a
+ * batch of writes in one call.
+ *
+ * The slice has view_parts = ks data parts (the columns of
+ * lizec_chunk_read_batch) and `rows` parity parts; chunk block c is row
+ * c / ks, column c % ks.  One write carries the new bytes [from, to) —
+ * size = to - from, the same range of every block (Operation::
+ * isExpandPossible, :57-71) — of chunk blocks [first_block, first_block +
+ * block_count).  For every block row b that the range touches, column c is,
+ * as `size` bytes,
+ *   - the new data, if chunk block b*ks + c lies in the range;
+ *   - else bytes [from, to) of block b of the data part behind column c as
+ *     it is now (fillStripe, :440-466) — a "fill";
+ *   - else zeros, if that part has no block b (:451, reed_solomon.h:79);
+ * and parity r of row b is row r of gftbls applied to those ks columns.
+ * gftbls is 32*ks*rows bytes, [row][column][32], one table per call:
+ * lizec_rs_encode_tables(k, m) for ec(k,m), ec_init_tables over ones for a
+ * xor slice.  Only [from, to) of anything is read or written.  The data
+ * packets are the caller's own bytes; the device work is the parity and the
+ * CRC of every packet, lizec_crc32(0, bytes, size). */
+typedef struct lizec_chunk_write {   /* 40 bytes, no padding */
+	uint64_t data;        /* address of the size bytes for block first_block;
+	                         block first_block+i at data + i*data_stride; any
+	                         alignment */
+	uint64_t crcs;        /* u32 array, 4-byte aligned, or 0 = no CRCs wanted */
+	uint32_t data_stride; /* >= size; unused if block_count == 1 */
+	uint32_t par_stride;  /* >= size; unused if the range touches one row */
+	uint32_t first_block, block_count;
+	uint32_t from, to;    /* 0 <= from < to <= 65536 */
+} lizec_chunk_write;
+
+/*  fill_dptrs[w][c], fill_nblocks[w][c]: address of block 0's data and block
+ *      count of the data part behind column c, by the ragged call's rules
+ *      (a count of 0 may come with address 0); the counts express the
+ *      chunk's current end.  Block b is read at fill + b*fill_block_stride +
+ *      from, only in rows the write touches and only for columns the range
+ *      does not cover there; a write of whole rows may pass all counts as 0.
+ *  fill_block_stride: >= 65536 (65536 MooseFS, 65540 INTERLEAVED).
+ *  par_dptrs[w][r]: address of the first byte written for parity r of the
+ *      FIRST touched row r0 = first_block / ks; row r0 + i goes to
+ *      + i*par_stride, size bytes each.  In place in an image: image block 0
+ *      + r0*stride + from, par_stride = the image's stride; a packet staging
+ *      buffer: its start, par_stride = size.  Any alignment.  0 = this
+ *      parity part is not wanted: nothing is computed for it and its CRC
+ *      slots are not written.
+ *  crcs[i], i < block_count: CRC of new block i; crcs[block_count + i*rows +
+ *      r]: CRC of parity r of touched row i; host order.
+ * Exactly the size bytes of each wanted parity row and the CRC slots are
+ * written.  Loads touch only aligned 16-byte units that hold a byte of a
+ * range.  A parity output must not overlap a data range, a fill range or
+ * another output of the call, and two writes that touch the same row do not
+ * belong in one call (canStartOperation, :345-355).  An operation with a hole
+ * inside a row is passed as its covering range.  A degraded slice is out of
+ * scope: rebuild a lost data part that a fill needs with
+ * lizec_chunk_read_batch first.
+ * Returns LIZEC_EINVAL from the host, with nothing enqueued and no byte
+ * written, for a NULL array; num_writes < 1; rows or view_parts outside
+ * 1..32; from >= to or to > 65536; block_count == 0 or first_block +
+ * block_count > 1048576; a data address of 0; a stride below size where the
+ * stride is used; fill_block_stride < 65536; a fill count above 32768, or a
+ * nonzero fill count with address 0; a crcs address that is not a multiple
+ * of 4; all parities of a write unwanted while crcs is 0; more than 2^31-1
+ * workgroups in a pass (one per 16 KiB tile of every touched row where a pass
+ * has up to 4 parities, per 8 KiB tile otherwise), or more than 2^24 CRCs.  A call in which every used address,
+ * every used stride, every `from` and every size is a multiple of 16 takes
+ * the aligned vector form.  Stream, thread and scratch contract as for the
+ * other batch calls. */
+int lizec_chunk_write_batch(lizec_engine *e, int rows, const uint8_t *gftbls,
+                            const lizec_chunk_write *writes, int num_writes,
+                            const uint64_t *fill_dptrs,
+                            const uint32_t *fill_nblocks, int view_parts,
+                            uint32_t fill_block_stride,
+                            const uint64_t *par_dptrs, void *stream);
+
+/* The same on the host: HOST addresses, no GPU.  Same refusals (nothing
+ * written), same bytes. */
+int lizec_chunk_write_host(int rows, const uint8_t *gftbls,
+                           const lizec_chunk_write *writes, int num_writes,
+                           const uint64_t *fill_ptrs,
+                           const uint32_t *fill_nblocks, int view_parts,
+                           uint32_t fill_block_stride,
+                           const uint64_t *par_ptrs);
+
 /* Per-block CRC32 over a contiguous device buffer:
  *  dev_crcs_out[b] = lizec_crc32(seed, dev_buf + b*block_len, block_len)
  * The chunkserver's per-64KiB-block gate (hddspacemgr.cc:1918-1920, scrub

@@ -13,6 +13,8 @@ package is the host-side mirror of the reference's EC surfaces:
   lizardfs_amd.chunkread    — the client read: block ranges of chunks
                               gathered from a slice's parts, lost parts
                               rebuilt on the way
+  lizardfs_amd.chunkwrite   — the client write: parity and packet CRCs of
+                              byte ranges written into a slice's blocks
   lizardfs_amd.writegate    — the batched hdd_write gate: byte-range data
                               and block CRC checks, new block CRCs
   lizardfs_amd.readgate     — the batched hdd_read gate: block CRC check and
@@ -29,6 +31,8 @@ from . import ec  # noqa: F401
 from . import crc  # noqa: F401
 from . import writegate  # noqa: F401
 from . import readgate  # noqa: F401
+from . import chunkwrite  # noqa: F401
 
-__all__ = ["slice_traits", "ec", "crc", "writegate", "readgate", "load_lib",
+__all__ = ["slice_traits", "ec", "crc", "writegate", "readgate", "chunkwrite",
+           "load_lib",
            "gpu_count", "LizecError"]

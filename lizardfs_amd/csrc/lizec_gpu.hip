@@ -47,6 +47,7 @@
 #include "crc_fold.h"
 #include "crc_ranges.h"
 #include "read_gate.h"
+#include "ec_kernel_write.h"
 
 /* Product kernel configuration (chosen by the variant A/B harness,
  * bench_variants.hip; numbers in profiles/ROUND1.md + ROUND2.md):
@@ -1930,6 +1931,195 @@ extern "C" int lizec_read_gate_batch(lizec_engine *e, const lizec_read_op *ops,
 		                   e->d_crc_const, e->d_crc_const + kCrcTabWords,
 		                   dev_status_out);
 	LIZEC_CHECK(hipGetLastError());
+	return LIZEC_OK;
+}
+
+/* ------------------------------------------------------------------ */
+/* Chunk writes: parity of byte ranges written into a slice's blocks,  */
+/* and the packets' CRCs (ec_kernel_write.h)                           */
+/* ------------------------------------------------------------------ */
+
+struct write_dev {
+	const uint8_t *tbls;
+	const uint4 *map16, *map8;   /* tile maps for 16 KiB / 8 KiB tiles */
+	uint32_t tiles16, tiles8;
+	const lizec_chunk_write *writes;
+	const uint64_t *fill, *par;
+	const uint32_t *fill_nb;
+};
+
+/* One pass of the write kernel: one workgroup per tile of the map that
+ * matches the pass's tile size. */
+template <int D>
+static void launch_chunk_write(int ks, int dest_base, int rows,
+                               const write_dev &w, uint32_t fill_stride,
+                               bool fast, hipStream_t s) {
+	constexpr int CH = ec_chunks_for(D);
+	const uint32_t total_tiles = CH == 4 ? w.tiles16 : w.tiles8;
+	const uint4 *map = CH == 4 ? w.map16 : w.map8;
+	size_t lds = (size_t)D * ks * kECTblBytes;
+#define LIZEC_LAUNCH_WRITE(FAST)                                            \
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(ec_chunk_write_kernel<D, CH, FAST>), \
+	                   dim3(total_tiles), dim3(kThreads), lds, s, ks,       \
+	                   dest_base, rows, w.tbls, map, w.writes, w.fill,      \
+	                   w.fill_nb, w.par, fill_stride)
+	if (fast) LIZEC_LAUNCH_WRITE(true);
+	else LIZEC_LAUNCH_WRITE(false);
+#undef LIZEC_LAUNCH_WRITE
+}
+
+extern "C" int64_t lizec_impl_chunk_write_check(
+    int rows, const uint8_t *gftbls, const lizec_chunk_write *writes,
+    int num_writes, const uint64_t *fill_ptrs, const uint32_t *fill_nblocks,
+    int view_parts, uint32_t fill_block_stride, const uint64_t *par_ptrs,
+    uint64_t *bits_out, uint64_t *tiles16_out, uint64_t *tiles8_out,
+    uint64_t *ncrc_out);
+
+extern "C" int lizec_chunk_write_batch(
+    lizec_engine *e, int rows, const uint8_t *gftbls,
+    const lizec_chunk_write *writes, int num_writes,
+    const uint64_t *fill_dptrs, const uint32_t *fill_nblocks, int view_parts,
+    uint32_t fill_block_stride, const uint64_t *par_dptrs, void *stream) {
+	if (!e) return LIZEC_EINVAL;
+	uint64_t bits, tiles16, tiles8, ncrc;
+	int64_t entries = lizec_impl_chunk_write_check(
+	    rows, gftbls, writes, num_writes, fill_dptrs, fill_nblocks, view_parts,
+	    fill_block_stride, par_dptrs, &bits, &tiles16, &tiles8, &ncrc);
+	if (entries <= 0) return LIZEC_EINVAL;
+	const bool fast = (bits & 15) == 0;
+	hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+	LIZEC_CHECK(hipSetDevice(e->device));
+
+	/* which tile sizes the passes use (ec_chunks_for): a last pass of up to
+	 * 4 rows cuts 16 KiB tiles, every other pass 8 KiB ones */
+	const int last = rows % 8 ? rows % 8 : 8;
+	const bool use16 = last <= 4, use8 = rows > 8 || last > 4;
+	/* the ragged call's scratch: table, tile maps, the writes, the fill
+	 * counts and the CRC lengths; every section 16-byte aligned.  The u64
+	 * scratch holds the fill and parity addresses, the CRC ranges'
+	 * addresses and result addresses, and the ranges kernel's results. */
+	auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+	const size_t W = (size_t)num_writes, ks = (size_t)view_parts;
+	const size_t nfill = W * ks, npar = W * rows;
+	size_t ntbl = ks * rows;   /* 32 B each */
+	size_t o_map16 = up16(ntbl * kECTblBytes);
+	size_t o_map8 = o_map16 + (use16 ? (size_t)tiles16 * 16 : 0);
+	size_t o_wr = o_map8 + (use8 ? (size_t)tiles8 * 16 : 0);
+	size_t o_fnb = o_wr + up16(W * sizeof(lizec_chunk_write));
+	size_t o_len = o_fnb + up16(nfill * 4);
+	size_t bytes = o_len + up16((size_t)ncrc * 4);
+	/* uploaded slots, and behind them the ranges kernel's results */
+	const size_t slots = nfill + npar + 2 * (size_t)ncrc;
+	lizec_stream_ctx *c;
+	int r = ctx_acquire_ragged(e, s, slots + ((size_t)ncrc + 1) / 2, slots * 8,
+	                           bytes, &c);
+	if (r != LIZEC_OK) return r;
+	uint8_t *h = c->h_ragged;
+	for (size_t i = 0; i < ntbl; ++i)
+		pack_mixed_radix(gftbls + i * 32, h + i * kECTblBytes);
+	memcpy(h + o_wr, writes, W * sizeof(lizec_chunk_write));
+	memcpy(h + o_fnb, fill_nblocks, nfill * 4);
+	uint64_t *pstage = (uint64_t *)(c->h_staging + (size_t)kECTblBytes * 32 * 32);
+	memcpy(pstage, fill_dptrs, nfill * 8);
+	memcpy(pstage + nfill, par_dptrs, npar * 8);
+	/* one host pass builds the tile maps and the CRC ranges: the new blocks,
+	 * then the wanted parities of every touched row */
+	uint32_t *m16 = (uint32_t *)(h + o_map16), *m8 = (uint32_t *)(h + o_map8);
+	uint32_t *lens = (uint32_t *)(h + o_len);
+	uint64_t *addrs = pstage + nfill + npar, *outs = addrs + ncrc;
+	size_t nr = 0;
+	for (size_t i = 0; i < W; ++i) {
+		const lizec_chunk_write &w = writes[i];
+		const uint32_t size = w.to - w.from;
+		const uint32_t r0 = w.first_block / (uint32_t)ks;
+		const uint32_t r1 = (w.first_block + w.block_count - 1) / (uint32_t)ks;
+		const uint64_t *pp = par_dptrs + i * rows;
+		if (w.crcs)
+			for (uint32_t b = 0; b < w.block_count; ++b) {
+				addrs[nr] = w.data + (b ? (uint64_t)b * w.data_stride : 0);
+				lens[nr] = size;
+				outs[nr++] = w.crcs + 4ull * b;
+			}
+		for (uint32_t b = r0; b <= r1; ++b) {
+			if (use16)
+				for (uint32_t t = 0; t * 16384u < size; ++t) {
+					*m16++ = (uint32_t)i;
+					*m16++ = b;
+					*m16++ = t;
+					*m16++ = b - r0;
+				}
+			if (use8)
+				for (uint32_t t = 0; t * 8192u < size; ++t) {
+					*m8++ = (uint32_t)i;
+					*m8++ = b;
+					*m8++ = t;
+					*m8++ = b - r0;
+				}
+			if (!w.crcs) continue;
+			for (int l = 0; l < rows; ++l) {
+				if (!pp[l]) continue;
+				addrs[nr] =
+				    pp[l] + (b > r0 ? (uint64_t)(b - r0) * w.par_stride : 0);
+				lens[nr] = size;
+				outs[nr++] = w.crcs + 4ull * (w.block_count +
+				                              (uint64_t)(b - r0) * rows + l);
+			}
+		}
+	}
+	(void)nr;   /* == ncrc: the check function counted the same ranges */
+	LIZEC_CHECK(hipMemcpyAsync(c->d_ragged, h, bytes, hipMemcpyHostToDevice, s));
+	LIZEC_CHECK(hipMemcpyAsync(c->d_ptrs, pstage, slots * 8,
+	                           hipMemcpyHostToDevice, s));
+	LIZEC_CHECK(hipEventRecord(c->uploaded, s));
+	c->ev_recorded = true;
+
+	write_dev wd;
+	wd.tbls = c->d_ragged;
+	wd.map16 = (const uint4 *)(c->d_ragged + o_map16);
+	wd.map8 = (const uint4 *)(c->d_ragged + o_map8);
+	wd.tiles16 = (uint32_t)tiles16;
+	wd.tiles8 = (uint32_t)tiles8;
+	wd.writes = (const lizec_chunk_write *)(c->d_ragged + o_wr);
+	wd.fill_nb = (const uint32_t *)(c->d_ragged + o_fnb);
+	wd.fill = c->d_ptrs;
+	wd.par = c->d_ptrs + nfill;
+	/* passes of at most 8 table rows, as run_batch_strided.  A write none of
+	 * whose parities is wanted still has tiles; they return at once. */
+	for (int base = 0; base < rows;) {
+		int d = rows - base;
+		if (d > 8) d = 8;
+#define LIZEC_LAUNCH_WRITE_D(D)                                            \
+	launch_chunk_write<D>(view_parts, base, rows, wd, fill_block_stride,   \
+	                      fast, s)
+		switch (d) {
+		case 1: LIZEC_LAUNCH_WRITE_D(1); break;
+		case 2: LIZEC_LAUNCH_WRITE_D(2); break;
+		case 3: LIZEC_LAUNCH_WRITE_D(3); break;
+		case 4: LIZEC_LAUNCH_WRITE_D(4); break;
+		case 5: LIZEC_LAUNCH_WRITE_D(5); break;
+		case 6: LIZEC_LAUNCH_WRITE_D(6); break;
+		case 7: LIZEC_LAUNCH_WRITE_D(7); break;
+		default: LIZEC_LAUNCH_WRITE_D(8); break;
+		}
+#undef LIZEC_LAUNCH_WRITE_D
+		base += d;
+	}
+	LIZEC_CHECK(hipGetLastError());
+	if (ncrc) {
+		/* behind the parity passes on the same stream: the parity ranges are
+		 * complete when the ranges kernel starts */
+		const uint32_t n = (uint32_t)ncrc;
+		uint32_t *d_crcs = (uint32_t *)(c->d_ptrs + nfill + npar + 2 * ncrc);
+		r = launch_crc_ranges(e, c->d_ptrs + nfill + npar,
+		                      (const uint32_t *)(c->d_ragged + o_len), n, 0u,
+		                      d_crcs, nullptr, s);
+		if (r != LIZEC_OK) return r;
+		hipLaunchKernelGGL(chunk_write_crc_scatter_kernel,
+		                   dim3((n + kCrcRangesThreads - 1) / kCrcRangesThreads),
+		                   dim3(kCrcRangesThreads), 0, s, d_crcs,
+		                   c->d_ptrs + nfill + npar + ncrc, n);
+		LIZEC_CHECK(hipGetLastError());
+	}
 	return LIZEC_OK;
 }
 

@@ -804,3 +804,147 @@ extern "C" int lizec_chunk_read_host(
 	}
 	return LIZEC_OK;
 }
+
+/* ------------------------------------------------------------------ */
+/* Batched chunk write: the checks and the host twin (pure host)      */
+/* ------------------------------------------------------------------ */
+
+static_assert(sizeof(lizec_chunk_write) == 40, "lizec_chunk_write has padding");
+
+/* The host checks of the chunk write, shared by lizec_chunk_write_host and
+ * lizec_chunk_write_batch (lizec_gpu.hip).  Returns the (write, block row)
+ * pairs that the ranges touch, or LIZEC_EINVAL.  *bits receives the OR of
+ * every used address and stride, every `from` and every size (low bits 0:
+ * the aligned kernel form); *tiles16 / *tiles8 the workgroups of a pass with
+ * 16 KiB / 8 KiB tiles; *ncrc the CRCs the call writes. */
+extern "C" int64_t lizec_impl_chunk_write_check(
+    int rows, const uint8_t *gftbls, const lizec_chunk_write *writes,
+    int num_writes, const uint64_t *fill_ptrs, const uint32_t *fill_nblocks,
+    int view_parts, uint32_t fill_block_stride, const uint64_t *par_ptrs,
+    uint64_t *bits_out, uint64_t *tiles16_out, uint64_t *tiles8_out,
+    uint64_t *ncrc_out) {
+	if (!gftbls || !writes || !fill_ptrs || !fill_nblocks || !par_ptrs)
+		return LIZEC_EINVAL;
+	if (num_writes < 1 || rows < 1 || rows > 32 || view_parts < 1 ||
+	    view_parts > 32)
+		return LIZEC_EINVAL;
+	if (fill_block_stride < 65536u) return LIZEC_EINVAL;
+	const uint32_t ks = (uint32_t)view_parts;
+	uint64_t bits = 0, entries = 0, tiles16 = 0, tiles8 = 0, ncrc = 0;
+	for (int i = 0; i < num_writes; ++i) {
+		const lizec_chunk_write &w = writes[i];
+		if (w.from >= w.to || w.to > 65536u) return LIZEC_EINVAL;
+		const uint32_t size = w.to - w.from;
+		const uint64_t first = w.first_block, count = w.block_count;
+		if (count == 0 || first + count > 1048576u) return LIZEC_EINVAL;
+		if (!w.data || (w.crcs & 3)) return LIZEC_EINVAL;
+		const uint64_t touched = (first + count - 1) / ks - first / ks + 1;
+		bits |= w.data | size | w.from;
+		if (count > 1) {
+			if (w.data_stride < size) return LIZEC_EINVAL;
+			bits |= w.data_stride;
+		}
+		if (touched > 1) {
+			if (w.par_stride < size) return LIZEC_EINVAL;
+			bits |= w.par_stride;
+		}
+		const uint64_t *fp = fill_ptrs + (size_t)i * ks;
+		const uint32_t *fn = fill_nblocks + (size_t)i * ks;
+		for (uint32_t c = 0; c < ks; ++c) {
+			if (fn[c] > 32768u) return LIZEC_EINVAL;
+			if (!fn[c]) continue;
+			if (!fp[c]) return LIZEC_EINVAL;
+			bits |= fp[c] | fill_block_stride;
+		}
+		uint32_t wanted = 0;
+		for (int r = 0; r < rows; ++r) {
+			const uint64_t p = par_ptrs[(size_t)i * rows + r];
+			if (!p) continue;
+			++wanted;
+			bits |= p;
+		}
+		if (!wanted && !w.crcs) return LIZEC_EINVAL;
+		entries += touched;
+		tiles16 += touched * ((size + 16383u) / 16384u);
+		tiles8 += touched * ((size + 8191u) / 8192u);
+		if (w.crcs) ncrc += count + touched * wanted;
+	}
+	/* the grids the passes launch (ec_chunks_for in lizec_gpu.hip): a last
+	 * pass of up to 4 rows cuts 16 KiB tiles, every other pass 8 KiB ones */
+	const int last = rows % 8 ? rows % 8 : 8;
+	const bool use16 = last <= 4, use8 = rows > 8 || last > 4;
+	if ((use16 && tiles16 > 0x7FFFFFFFull) || (use8 && tiles8 > 0x7FFFFFFFull))
+		return LIZEC_EINVAL;
+	/* crc32_ranges_kernel's bound */
+	if (ncrc > ((uint64_t)1 << 24)) return LIZEC_EINVAL;
+	if (bits_out) *bits_out = bits;
+	if (tiles16_out) *tiles16_out = tiles16;
+	if (tiles8_out) *tiles8_out = tiles8;
+	if (ncrc_out) *ncrc_out = ncrc;
+	return (int64_t)entries;
+}
+
+/* ChunkWriter::startOperation over host memory, row by row: the columns are
+ * pointed at the new data, the fill or a block of zeros, ec_encode_data
+ * computes the wanted parities over [from, to), lizec_crc32 the packets'
+ * CRCs; see lizec.h. */
+extern "C" int lizec_chunk_write_host(
+    int rows, const uint8_t *gftbls, const lizec_chunk_write *writes,
+    int num_writes, const uint64_t *fill_ptrs, const uint32_t *fill_nblocks,
+    int view_parts, uint32_t fill_block_stride, const uint64_t *par_ptrs) {
+	int64_t entries = lizec_impl_chunk_write_check(
+	    rows, gftbls, writes, num_writes, fill_ptrs, fill_nblocks, view_parts,
+	    fill_block_stride, par_ptrs, nullptr, nullptr, nullptr, nullptr);
+	if (entries < 0) return (int)entries;
+	lizec_crc32_init();
+	const uint32_t ks = (uint32_t)view_parts;
+	static const uint8_t zeros[65536] = {0};
+	uint8_t tbl[32 * 32 * 32];   /* the wanted rows, closed up */
+	for (int i = 0; i < num_writes; ++i) {
+		const lizec_chunk_write &w = writes[i];
+		const uint32_t size = w.to - w.from;
+		const uint32_t first = w.first_block, end = first + w.block_count;
+		const uint64_t *fp = fill_ptrs + (size_t)i * ks;
+		const uint32_t *fn = fill_nblocks + (size_t)i * ks;
+		const uint64_t *pp = par_ptrs + (size_t)i * rows;
+		const uint8_t *data = (const uint8_t *)(uintptr_t)w.data;
+		/* unused, and unchecked, for a single block */
+		const uint64_t dstride = w.block_count > 1 ? w.data_stride : 0;
+		uint32_t *crcs = (uint32_t *)(uintptr_t)w.crcs;
+		int want_row[32], nw = 0;
+		for (int r = 0; r < rows; ++r)
+			if (pp[r]) {
+				memcpy(tbl + (size_t)nw * ks * 32, gftbls + (size_t)r * ks * 32,
+				       (size_t)ks * 32);
+				want_row[nw++] = r;
+			}
+		if (crcs)
+			for (uint32_t b = 0; b < w.block_count; ++b)
+				crcs[b] = lizec_crc32(0, data + b * dstride, size);
+		if (!nw) continue;
+		const uint32_t r0 = first / ks;
+		for (uint32_t b = r0; b <= (end - 1) / ks; ++b) {
+			uint8_t *in[32], *out[32];
+			for (uint32_t c = 0; c < ks; ++c) {
+				const uint32_t cb = b * ks + c;
+				if (cb >= first && cb < end)
+					in[c] = (uint8_t *)data + (cb - first) * dstride;
+				else if (b < fn[c])
+					in[c] = (uint8_t *)(uintptr_t)fp[c] +
+					        (uint64_t)b * fill_block_stride + w.from;
+				else
+					in[c] = (uint8_t *)zeros;
+			}
+			const uint64_t poff =
+			    b > r0 ? (uint64_t)(b - r0) * w.par_stride : 0;
+			for (int l = 0; l < nw; ++l)
+				out[l] = (uint8_t *)(uintptr_t)pp[want_row[l]] + poff;
+			ec_encode_data((int)size, (int)ks, nw, tbl, in, out);
+			if (crcs)
+				for (int l = 0; l < nw; ++l)
+					crcs[w.block_count + (size_t)(b - r0) * rows + want_row[l]] =
+					    lizec_crc32(0, out[l], size);
+		}
+	}
+	return LIZEC_OK;
+}

@@ -178,6 +178,14 @@ def lib():
         [ctypes.c_void_p]
     L.lizec_chunk_read_host.restype = ctypes.c_int
     L.lizec_chunk_read_host.argtypes = read_args
+    write_args = [
+        ctypes.c_int, u8p, ctypes.c_void_p, ctypes.c_int, u64p, u32p,
+        ctypes.c_int, ctypes.c_uint32, u64p]
+    L.lizec_chunk_write_batch.restype = ctypes.c_int
+    L.lizec_chunk_write_batch.argtypes = [ctypes.c_void_p] + write_args + \
+        [ctypes.c_void_p]
+    L.lizec_chunk_write_host.restype = ctypes.c_int
+    L.lizec_chunk_write_host.argtypes = write_args
     _lib = L
     return _lib
 
