@@ -453,6 +453,68 @@ int lizec_chunk_read_host(int srcs, int rows, const uint8_t *gftbls,
                           uint32_t src_block_stride,
                           uint32_t dst_block_stride);
 
+/* The VERIFIED chunk read — lizec_chunk_read_batch with the check that the
+ * reference's client makes before it decodes anything: every received 64 KiB
+ * block is compared with the CRC that came with it
+ * (ReadOperationExecutor, read_operation_executor.cc:261-263:
+ * mycrc32(0, block, MFSBLOCKSIZE)), and a part with a bad block is recorded
+ * (ChunkReader::readData, chunk_reader.cc:135-137, crcErrors_) so that the
+ * next plan leaves it out (:63-65).  Every argument up to dst_block_stride
+ * is lizec_chunk_read_batch's, with the same meaning.
+ *  crc_dptrs  : HOST array [num_reads][srcs]: device address of the CRC of
+ *             the slot's block 0, any alignment; 0 = the slot is not
+ *             verified (it is copied and used as it is).
+ *  crc_block_stride: >= 4; the CRC of the slot's block b is the 4 bytes,
+ *             big-endian, at crc + b*crc_block_stride.  4 for a CRC array
+ *             (MooseFS header order); 65540 with crc = data - 4 for an
+ *             INTERLEAVED image or a stream of whole-block READ_DATA packets
+ *             (what lizec_read_gate_batch emits).
+ *  dev_bad_out: device u32[num_reads]: bit j is set iff a checked block of
+ *             slot j failed.  Every entry is written, 0 for a clean read.
+ * Which blocks are checked: block b of slot j iff the slot has a CRC
+ * address, b < src_nblocks[read][j], and the read loads the block — the
+ * column the slot backs is requested in row b, or some lost column is.  A
+ * row without a lost requested column thus checks just its requested
+ * columns, a row with one checks every present slot, and blocks at or past
+ * a part's count are never checked.  Each such block is checked exactly
+ * once; of any other block no data byte and no CRC byte is read.  There is
+ * no sparse-block rule (a stored CRC of 0 is compared like any other): that
+ * rule is the chunkserver's (hddspacemgr.cc:1556-1596).
+ * Order on the stream: dev_bad_out is zeroed, the verify kernel runs (one
+ * wave per (read, block row, slot), hash only: csrc/read_verify.h), then
+ * exactly the launches of lizec_chunk_read_batch.  The output bytes are
+ * therefore written WHETHER OR NOT a check fails — the verdict is known only
+ * after the pass, as for the read gate.  THE CALLER MUST DISCARD THE OUTPUT
+ * OF A READ WHOSE MASK IS NOT 0, drop the flagged parts and read again.
+ * Scratch cost: that of lizec_chunk_read_batch plus 8 bytes per source slot
+ * (the CRC addresses, staged behind the destination addresses), device and
+ * pinned host each: 24 bytes per source slot in all.
+ * Returns LIZEC_EINVAL from the host, with nothing enqueued and no byte
+ * written (dev_bad_out included), for everything lizec_chunk_read_batch
+ * refuses, a NULL crc_dptrs or dev_bad_out, or crc_block_stride < 4.
+ * Stream and thread contract as for the other batch calls. */
+int lizec_chunk_read_verified_batch(
+    lizec_engine *e, int srcs, int rows, const uint8_t *gftbls, int ntables,
+    const uint32_t *tbl_index, const uint64_t *src_dptrs,
+    const uint32_t *src_nblocks, int view_parts, const uint8_t *col_map,
+    const uint32_t *first_block, const uint32_t *block_count,
+    const uint64_t *dst_dptrs, int num_reads, uint32_t src_block_stride,
+    uint32_t dst_block_stride, const uint64_t *crc_dptrs,
+    uint32_t crc_block_stride, uint32_t *dev_bad_out, void *stream);
+
+/* The same on the host: every address is a HOST address, bad_out a host
+ * array u32[num_reads]; lizec_crc32 over the same blocks by the same rule,
+ * then lizec_chunk_read_host.  Same refusals (nothing written), same bytes,
+ * same masks. */
+int lizec_chunk_read_verified_host(
+    int srcs, int rows, const uint8_t *gftbls, int ntables,
+    const uint32_t *tbl_index, const uint64_t *src_ptrs,
+    const uint32_t *src_nblocks, int view_parts, const uint8_t *col_map,
+    const uint32_t *first_block, const uint32_t *block_count,
+    const uint64_t *dst_ptrs, int num_reads, uint32_t src_block_stride,
+    uint32_t dst_block_stride, const uint64_t *crc_ptrs,
+    uint32_t crc_block_stride, uint32_t *bad_out);
+
 /* The CLIENT WRITE of an EC or xor slice: ChunkWriter::startOperation
  * (mount/chunk_writer.cc:475-547) with computeParityBlock (:365-402) and the
  * CRCs of WriteExecutor::addDataPacket (write_executor.cc:91-107), for a

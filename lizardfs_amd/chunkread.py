@@ -88,9 +88,14 @@ class _Batch:
 
 
 def _prepare(slice_type, fragments, geom, chunk_blocks, first_block,
-             block_count, erased, src_stride, dst_stride):
+             block_count, erased, src_stride, dst_stride, only=None):
     """geom(fragment, what) -> (rows, row bytes, row stride, address), or
-    ValueError.  Touches neither the library nor a GPU."""
+    ValueError.  Touches neither the library nor a GPU.
+
+    only: the chunks that the batch is to hold (a retry round of
+    read_chunks_verified).  Everything is still checked for all S chunks,
+    but a chunk of `only` that cannot be read is listed in .dead, not
+    raised."""
     _check_slice(slice_type, "slice_type")
     cb = np.asarray(chunk_blocks)
     if cb.ndim != 1 or cb.size < 1 or cb.dtype.kind not in "iu":
@@ -129,19 +134,23 @@ def _prepare(slice_type, fragments, geom, chunk_blocks, first_block,
             raise ValueError(f"erased[{s}]: part index out of [0, {nparts})")
         gone.append(set(e))
     there = [p for p in range(nparts) if fragments[p] is not None]
-    plans, seen = [], {}
-    for s in range(S):
+    plans, seen, live, dead = [], {}, [], []
+    for s in (range(S) if only is None else only):
         # a batch repeats few patterns: plan each once
         key = (frozenset(gone[s]), int(first[s]), int(count[s]))
         if key not in seen:
             seen[key] = plan_read(
                 slice_type, [p for p in there if p not in gone[s]],
                 int(first[s]), int(count[s]))
+        if seen[key] is None and only is not None:
+            dead.append(s)
+            continue
         if seen[key] is None:
             raise ValueError(f"chunk {s}: blocks [{first[s]}, "
                              f"{first[s] + count[s]}) cannot be read from "
                              f"the parts that are left")
         plans.append(seen[key])
+        live.append(s)
     counts = {int(n): [_part_blocks(slice_type, p, int(n))
                        for p in range(nparts)] for n in np.unique(cb)}
     src_nb = np.array([counts[int(n)] for n in cb], np.int64)
@@ -162,22 +171,26 @@ def _prepare(slice_type, fragments, geom, chunk_blocks, first_block,
                              f"aligned")
         bases[p], strides[p] = addr, rstride
 
+    # b.S reads, read i on chunk b.chunks[i]: all S chunks unless `only`
     b = _Batch()
-    b.S, b.slice_type, b.plans = S, slice_type, plans
+    b.S, b.slice_type, b.plans = len(live), slice_type, plans
+    b.chunks, b.dead, b.gone = live, dead, gone
+    b.part_top = src_nb.max(axis=0)
     b.ks = st.data_parts(slice_type)
     b.srcs = b.ks          # ec: k survivors; xorN: the N others; standard: 1
-    b.rows = max(len(p.lost) for p in plans)
-    b.first, b.count = first.astype(np.uint32), count.astype(np.uint32)
-    b.src_ptrs = np.zeros((S, b.srcs), np.uint64)
-    b.src_nb = np.zeros((S, b.srcs), np.uint32)
-    b.col_map = np.full((S, b.ks), UNMAPPED, np.uint8)
-    for s, plan in enumerate(plans):
+    b.rows = max((len(p.lost) for p in plans), default=0)
+    b.first = first[live].astype(np.uint32)
+    b.count = count[live].astype(np.uint32)
+    b.src_ptrs = np.zeros((b.S, b.srcs), np.uint64)
+    b.src_nb = np.zeros((b.S, b.srcs), np.uint32)
+    b.col_map = np.full((b.S, b.ks), UNMAPPED, np.uint8)
+    for i, (s, plan) in enumerate(zip(live, plans)):
         for j, p in enumerate(plan.parts):
             # a part that holds no block of a short chunk keeps its address:
             # a requested column may be mapped to it and reads as zeros
-            b.src_ptrs[s, j] = bases[p] + np.uint64(s) * strides[p]
-            b.src_nb[s, j] = src_nb[s, p]
-        b.col_map[s] = plan.col_map
+            b.src_ptrs[i, j] = bases[p] + np.uint64(s) * strides[p]
+            b.src_nb[i, j] = src_nb[s, p]
+        b.col_map[i] = plan.col_map
     b.src_stride, b.dst_stride = src_stride, dst_stride
     b.need = (int(count.max()) - 1) * dst_stride + _BLOCK
     return b
@@ -305,3 +318,216 @@ def read_chunks_host(slice_type, fragments, chunk_blocks, first_block,
     L.check(_call(L.lib().lizec_chunk_read_host, (), b, dst, ()),
             "lizec_chunk_read_host")
     return out
+
+
+# ---- the verified read -------------------------------------------------------
+
+_INLINE = _BLOCK + 4    # [4-byte CRC][block]: INTERLEAVED images, READ_DATA
+
+VerifiedRead = collections.namedtuple("VerifiedRead", "out corrupt unreadable")
+VerifiedRead.__doc__ = """What read_chunks_verified returns:
+  out        — as read_chunks;
+  corrupt    — per chunk, the sorted tuple of parts that failed a CRC check
+               (what the reference collects in crcErrors_);
+  unreadable — per chunk, True where the parts that are left cannot serve
+               the range; such a row's contents are unspecified."""
+
+
+def _verified(slice_type, fragments, crcs, geom, chunk_blocks, first_block,
+              block_count, erased, src_stride, dst_stride, inline_crcs,
+              retry, make_out, run):
+    """The rounds of a verified read over tensors or arrays.
+    make_out(batch) -> (out, address of row 0, row stride);
+    run(batch, dst, crc_ptrs, crc_stride) -> the masks, one per read, as a
+    numpy array — it waits for them."""
+    _check_slice(slice_type, "slice_type")
+    nparts = _total_parts(slice_type)
+    fragments = list(fragments)
+    if inline_crcs:
+        if crcs is not None:
+            raise ValueError("inline_crcs: the CRCs lie in the fragments, "
+                             "crcs must be None")
+        if src_stride < _INLINE:
+            raise ValueError(f"inline_crcs needs src_stride >= {_INLINE}")
+        crcs = [None] * nparts
+
+        def data_geom(t, what):
+            s, span, rstride, addr = geom(t, what)
+            return s, span - 4, rstride, addr + 4
+    else:
+        crcs = list(crcs) if crcs is not None else None
+        if crcs is None or len(crcs) != nparts:
+            raise ValueError(f"need {nparts} crcs entries (None = part not "
+                             f"verified) for slice type {slice_type}")
+        data_geom = geom
+    args = (slice_type, fragments, data_geom, chunk_blocks, first_block,
+            block_count)
+    b = _prepare(*args, erased, src_stride, dst_stride)
+    S = b.S
+    # where the CRC of block 0 of part p of chunk s lies: base + s * stride
+    crc_base = np.zeros(nparts, np.uint64)
+    crc_rstride = np.zeros(nparts, np.uint64)
+    for p in range(nparts):
+        if inline_crcs and fragments[p] is not None:
+            _, _, rstride, addr = geom(fragments[p], f"fragment {p}")
+            crc_base[p], crc_rstride[p] = addr, rstride
+        elif crcs[p] is not None:
+            s, span, rstride, addr = geom(crcs[p], f"crcs[{p}]")
+            if s != S or span < 4 * int(b.part_top[p]):
+                raise ValueError(f"crcs[{p}] must hold [S={S}, "
+                                 f"{4 * int(b.part_top[p])}] bytes")
+            crc_base[p], crc_rstride[p] = addr, rstride
+    crc_stride = src_stride if inline_crcs else 4
+    out, out_addr, out_rstride = make_out(b)
+
+    gone = [set(g) for g in b.gone]
+    corrupt = [set() for _ in range(S)]
+    unreadable = [False] * S
+    while b.S:
+        chunks = np.array(b.chunks, np.uint64)
+        dst = np.uint64(out_addr) + chunks * np.uint64(out_rstride)
+        crc_ptrs = np.zeros((b.S, b.srcs), np.uint64)
+        for i, (s, plan) in enumerate(zip(b.chunks, b.plans)):
+            for j, p in enumerate(plan.parts):
+                if crc_base[p]:
+                    crc_ptrs[i, j] = crc_base[p] + np.uint64(s) * crc_rstride[p]
+        masks = run(b, dst, crc_ptrs, crc_stride)
+        again = []
+        for s, plan, mask in zip(b.chunks, b.plans, masks):
+            if not mask:
+                continue
+            bad = [p for j, p in enumerate(plan.parts) if (int(mask) >> j) & 1]
+            corrupt[s].update(bad)
+            gone[s].update(bad)          # chunk_reader.cc:63-65
+            if retry:
+                again.append(s)
+            else:
+                unreadable[s] = True
+        if not again:
+            break
+        b = _prepare(*args, gone, src_stride, dst_stride, only=again)
+        for s in b.dead:
+            unreadable[s] = True
+    return VerifiedRead(out, [tuple(sorted(c)) for c in corrupt], unreadable)
+
+
+def _verified_call(fn, head, b, dst, crc_ptrs, crc_stride, bad, tail):
+    crc_ptrs = np.ascontiguousarray(crc_ptrs, np.uint64)
+    return _call(fn, head, b, dst,
+                 (crc_ptrs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                  crc_stride, bad) + tail)
+
+
+def read_chunks_verified(slice_type, fragments, crcs, chunk_blocks,
+                         first_block, block_count, erased=None, out=None,
+                         src_stride=_BLOCK, dst_stride=_BLOCK,
+                         inline_crcs=False, retry=True, device=0):
+    """read_chunks with the client's CRC check and its retry: every source
+    block a read consumes is compared with its CRC
+    (lizec_chunk_read_verified_batch; read_operation_executor.cc:261-263),
+    the parts that fail are dropped from the chunk's available parts
+    (chunk_reader.cc:63-65), and the chunk is planned and read again from
+    what is left.
+
+    fragments, chunk_blocks, first_block, block_count, erased, out,
+    src_stride, dst_stride: as read_chunks.
+    crcs: one entry per part: None (the part is not verified) or a
+      [S, >= 4*blocks] CUDA uint8 row view with the big-endian CRC of the
+      part's block b at 4*b.
+    inline_crcs: crcs must be None and src_stride >= 65540; every fragment
+      row then starts at the CRC of block 0 — an INTERLEAVED part image's
+      body, or readgate.read_packets output for whole blocks: block b's CRC
+      at b*src_stride, its data at 4 + b*src_stride.
+    retry: False = one round; a chunk with a bad part is then reported
+      unreadable.
+
+    Round 0 reads every chunk; each later round holds only the chunks whose
+    last round found a bad part and that can still be planned, written to
+    the same rows of out.  Every retried chunk has lost at least one more
+    part, so there are at most as many rounds as the slice has parts.
+
+    This function is SYNCHRONOUS: after each round it waits for the masks on
+    the host, since the next round's plans depend on them.
+
+    Returns VerifiedRead(out, corrupt, unreadable).  Raises ValueError,
+    before any GPU use, for everything read_chunks raises it for (a read
+    that the parts cannot serve before any check is one of them), for a
+    crcs entry of the wrong shape, dtype, device or row count, and for
+    inline_crcs with crcs given or a stride below 65540.
+    """
+    import torch
+
+    def geom(t, what):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or \
+                not t.is_cuda or t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f"{what} must be a CUDA uint8 [S, L] tensor "
+                             f"with contiguous rows")
+        return t.shape[0], t.shape[1], t.stride(0), t.data_ptr()
+
+    def make_out(b):
+        o = out
+        if o is None:
+            dev = next(t for t in fragments if t is not None).device
+            o = torch.empty((b.S, b.need), dtype=torch.uint8, device=dev)
+        else:
+            s, span, rstride, addr = geom(o, "out")
+            if s != b.S or span < b.need:
+                raise ValueError(f"out must hold [S={b.S}, {b.need}] bytes")
+            if addr % 4 or (s > 1 and rstride % 4):
+                raise ValueError("out: block data must be 4-byte aligned")
+        return o, o.data_ptr(), o.stride(0)
+
+    def run(b, dst, crc_ptrs, crc_stride):
+        bad = torch.empty(b.S, dtype=torch.int32,
+                          device=torch.device("cuda", device))
+        stream = ctypes.c_void_p(
+            torch.cuda.current_stream(device).cuda_stream)
+        L.check(_verified_call(
+            L.lib().lizec_chunk_read_verified_batch, (L.engine(device),), b,
+            dst, crc_ptrs, crc_stride, ctypes.c_void_p(bad.data_ptr()),
+            (stream,)), "lizec_chunk_read_verified_batch")
+        return bad.cpu().numpy().view(np.uint32)   # waits for the stream
+
+    return _verified(slice_type, fragments, crcs, geom, chunk_blocks,
+                     first_block, block_count, erased, src_stride,
+                     dst_stride, inline_crcs, retry, make_out, run)
+
+
+def read_chunks_verified_host(slice_type, fragments, crcs, chunk_blocks,
+                              first_block, block_count, erased=None,
+                              out=None, src_stride=_BLOCK, dst_stride=_BLOCK,
+                              inline_crcs=False, retry=True):
+    """read_chunks_verified over numpy arrays, through
+    lizec_chunk_read_verified_host: no GPU is needed.  fragments, crcs and
+    out are uint8 [S, L] arrays with contiguous rows; a fresh out is
+    zero-filled."""
+    def geom(a, what):
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or \
+                a.ndim != 2 or a.strides[1] != 1:
+            raise ValueError(f"{what} must be a uint8 [S, L] array with "
+                             f"contiguous rows")
+        return a.shape[0], a.shape[1], a.strides[0], a.ctypes.data
+
+    def make_out(b):
+        o = out
+        if o is None:
+            o = np.zeros((b.S, b.need), np.uint8)
+        else:
+            s, span, rstride, addr = geom(o, "out")
+            if s != b.S or span < b.need or not o.flags.writeable:
+                raise ValueError(f"out must hold [S={b.S}, {b.need}] bytes")
+            if addr % 4 or (s > 1 and rstride % 4):
+                raise ValueError("out: block data must be 4-byte aligned")
+        return o, o.ctypes.data, o.strides[0]
+
+    def run(b, dst, crc_ptrs, crc_stride):
+        bad = np.zeros(b.S, np.uint32)
+        L.check(_verified_call(
+            L.lib().lizec_chunk_read_verified_host, (), b, dst, crc_ptrs,
+            crc_stride, ctypes.c_void_p(bad.ctypes.data), ()),
+            "lizec_chunk_read_verified_host")
+        return bad
+
+    return _verified(slice_type, fragments, crcs, geom, chunk_blocks,
+                     first_block, block_count, erased, src_stride,
+                     dst_stride, inline_crcs, retry, make_out, run)

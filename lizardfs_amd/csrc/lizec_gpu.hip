@@ -47,6 +47,7 @@
 #include "crc_fold.h"
 #include "crc_ranges.h"
 #include "read_gate.h"
+#include "read_verify.h"
 #include "ec_kernel_write.h"
 
 /* Product kernel configuration (chosen by the variant A/B harness,
@@ -1241,13 +1242,17 @@ extern "C" int64_t lizec_impl_chunk_read_check(
     const uint64_t *dst_dptrs, int num_reads, uint32_t src_block_stride,
     uint32_t dst_block_stride, uint64_t *sbits_out, uint64_t *dbits_out);
 
-extern "C" int lizec_chunk_read_batch(
+/* The body of lizec_chunk_read_batch and lizec_chunk_read_verified_batch.
+ * With crc_dptrs the sources are checked first (read_verify.h): dev_bad is
+ * zeroed, the verify kernel runs, then the launches of the plain read. */
+static int chunk_read_run(
     lizec_engine *e, int srcs, int rows, const uint8_t *gftbls, int ntables,
     const uint32_t *tbl_index, const uint64_t *src_dptrs,
     const uint32_t *src_nblocks, int view_parts, const uint8_t *col_map,
     const uint32_t *first_block, const uint32_t *block_count,
     const uint64_t *dst_dptrs, int num_reads, uint32_t src_block_stride,
-    uint32_t dst_block_stride, void *stream) {
+    uint32_t dst_block_stride, const uint64_t *crc_dptrs,
+    uint32_t crc_block_stride, uint32_t *dev_bad, void *stream) {
 	if (!e) return LIZEC_EINVAL;
 	uint64_t sbits, dbits;
 	int64_t entries = lizec_impl_chunk_read_check(
@@ -1273,8 +1278,11 @@ extern "C" int lizec_chunk_read_batch(
 	size_t o_range = o_rcol + up16(nrow * 4);
 	size_t bytes = o_range + up16(R * 8);
 	lizec_stream_ctx *c;
-	int r = ctx_acquire_ragged(e, s, nsrc + R, (nsrc + R) * 8, bytes, &c);
+	/* a verified read stages the CRC addresses behind the destinations */
+	const size_t nptr = nsrc + R + (crc_dptrs ? nsrc : 0);
+	int r = ctx_acquire_ragged(e, s, nptr, nptr * 8, bytes, &c);
 	if (r != LIZEC_OK) return r;
+	if (crc_dptrs) LIZEC_CHECK(hipMemsetAsync(dev_bad, 0, R * 4, s));
 	uint8_t *h = c->h_ragged;
 	for (size_t i = 0; i < ntbl; ++i)
 		pack_mixed_radix(gftbls + i * 32, h + i * kECTblBytes);
@@ -1310,8 +1318,9 @@ extern "C" int lizec_chunk_read_batch(
 	uint64_t *pstage = (uint64_t *)(c->h_staging + (size_t)kECTblBytes * 32 * 32);
 	memcpy(pstage, src_dptrs, nsrc * 8);
 	memcpy(pstage + nsrc, dst_dptrs, R * 8);
+	if (crc_dptrs) memcpy(pstage + nsrc + R, crc_dptrs, nsrc * 8);
 	LIZEC_CHECK(hipMemcpyAsync(c->d_ragged, h, bytes, hipMemcpyHostToDevice, s));
-	LIZEC_CHECK(hipMemcpyAsync(c->d_ptrs, pstage, (nsrc + R) * 8,
+	LIZEC_CHECK(hipMemcpyAsync(c->d_ptrs, pstage, nptr * 8,
 	                           hipMemcpyHostToDevice, s));
 	LIZEC_CHECK(hipEventRecord(c->uploaded, s));
 	c->ev_recorded = true;
@@ -1327,6 +1336,18 @@ extern "C" int lizec_chunk_read_batch(
 	rd.src = c->d_ptrs;
 	rd.dst = c->d_ptrs + nsrc;
 	rd.view_parts = (uint32_t)view_parts;
+	if (crc_dptrs) {
+		/* one wave per (map entry, slot), four per workgroup: at most
+		 * entries * 8 workgroups, which the check bounds by 2^31 - 1 */
+		const uint64_t items = (uint64_t)entries * srcs;
+		hipLaunchKernelGGL(chunk_read_verify_kernel,
+		                   dim3((uint32_t)((items + 3) / 4)),
+		                   dim3(kCrcRangesThreads), 0, s, srcs, rows, items,
+		                   rd.map, rd.src, c->d_ptrs + nsrc + R, rd.src_nb,
+		                   rd.slot_col, rd.row_col, rd.view_parts, rd.range,
+		                   src_block_stride, crc_block_stride, e->d_crc_const,
+		                   e->d_crc_const + kCrcTabWords, dev_bad);
+	}
 	/* passes of at most 8 table rows, as run_batch_strided; pass 0 copies */
 	if (rows == 0)
 		launch_chunk_read<0>((uint32_t)entries, srcs, 0, 0, rd,
@@ -1352,6 +1373,35 @@ extern "C" int lizec_chunk_read_batch(
 	}
 	LIZEC_CHECK(hipGetLastError());
 	return LIZEC_OK;
+}
+
+extern "C" int lizec_chunk_read_batch(
+    lizec_engine *e, int srcs, int rows, const uint8_t *gftbls, int ntables,
+    const uint32_t *tbl_index, const uint64_t *src_dptrs,
+    const uint32_t *src_nblocks, int view_parts, const uint8_t *col_map,
+    const uint32_t *first_block, const uint32_t *block_count,
+    const uint64_t *dst_dptrs, int num_reads, uint32_t src_block_stride,
+    uint32_t dst_block_stride, void *stream) {
+	return chunk_read_run(e, srcs, rows, gftbls, ntables, tbl_index, src_dptrs,
+	                      src_nblocks, view_parts, col_map, first_block,
+	                      block_count, dst_dptrs, num_reads, src_block_stride,
+	                      dst_block_stride, nullptr, 0, nullptr, stream);
+}
+
+extern "C" int lizec_chunk_read_verified_batch(
+    lizec_engine *e, int srcs, int rows, const uint8_t *gftbls, int ntables,
+    const uint32_t *tbl_index, const uint64_t *src_dptrs,
+    const uint32_t *src_nblocks, int view_parts, const uint8_t *col_map,
+    const uint32_t *first_block, const uint32_t *block_count,
+    const uint64_t *dst_dptrs, int num_reads, uint32_t src_block_stride,
+    uint32_t dst_block_stride, const uint64_t *crc_dptrs,
+    uint32_t crc_block_stride, uint32_t *dev_bad_out, void *stream) {
+	if (!crc_dptrs || !dev_bad_out || crc_block_stride < 4) return LIZEC_EINVAL;
+	return chunk_read_run(e, srcs, rows, gftbls, ntables, tbl_index, src_dptrs,
+	                      src_nblocks, view_parts, col_map, first_block,
+	                      block_count, dst_dptrs, num_reads, src_block_stride,
+	                      dst_block_stride, crc_dptrs, crc_block_stride,
+	                      dev_bad_out, stream);
 }
 
 /* Multi-table launch: same grid/tile/LDS shape as launch_ec. */

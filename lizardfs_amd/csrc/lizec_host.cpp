@@ -736,18 +736,12 @@ extern "C" int64_t lizec_impl_chunk_read_check(
 /* ChunkReader::readData over host memory, row by row: memcpy for the
  * columns a source backs, ec_encode_data over the present sources for the
  * lost ones; see lizec.h. */
-extern "C" int lizec_chunk_read_host(
-    int srcs, int rows, const uint8_t *gftbls, int ntables,
-    const uint32_t *tbl_index, const uint64_t *src_ptrs,
-    const uint32_t *src_nblocks, int view_parts, const uint8_t *col_map,
-    const uint32_t *first_block, const uint32_t *block_count,
-    const uint64_t *dst_ptrs, int num_reads, uint32_t src_block_stride,
-    uint32_t dst_block_stride) {
-	int64_t entries = lizec_impl_chunk_read_check(
-	    srcs, rows, gftbls, ntables, tbl_index, src_ptrs, src_nblocks,
-	    view_parts, col_map, first_block, block_count, dst_ptrs, num_reads,
-	    src_block_stride, dst_block_stride, nullptr, nullptr);
-	if (entries < 0) return (int)entries;
+static void chunk_read_host_run(
+    int srcs, int rows, const uint8_t *gftbls, const uint32_t *tbl_index,
+    const uint64_t *src_ptrs, const uint32_t *src_nblocks, int view_parts,
+    const uint8_t *col_map, const uint32_t *first_block,
+    const uint32_t *block_count, const uint64_t *dst_ptrs, int num_reads,
+    uint32_t src_block_stride, uint32_t dst_block_stride) {
 	const uint32_t ks = (uint32_t)view_parts;
 	uint8_t tbl[32 * 32 * 32];   /* the lost rows over the present sources */
 	for (int i = 0; i < num_reads; ++i) {
@@ -802,6 +796,79 @@ extern "C" int lizec_chunk_read_host(
 			ec_encode_data(65536, np, nl, tbl, in, lost);
 		}
 	}
+}
+
+extern "C" int lizec_chunk_read_host(
+    int srcs, int rows, const uint8_t *gftbls, int ntables,
+    const uint32_t *tbl_index, const uint64_t *src_ptrs,
+    const uint32_t *src_nblocks, int view_parts, const uint8_t *col_map,
+    const uint32_t *first_block, const uint32_t *block_count,
+    const uint64_t *dst_ptrs, int num_reads, uint32_t src_block_stride,
+    uint32_t dst_block_stride) {
+	int64_t entries = lizec_impl_chunk_read_check(
+	    srcs, rows, gftbls, ntables, tbl_index, src_ptrs, src_nblocks,
+	    view_parts, col_map, first_block, block_count, dst_ptrs, num_reads,
+	    src_block_stride, dst_block_stride, nullptr, nullptr);
+	if (entries < 0) return (int)entries;
+	chunk_read_host_run(srcs, rows, gftbls, tbl_index, src_ptrs, src_nblocks,
+	                    view_parts, col_map, first_block, block_count, dst_ptrs,
+	                    num_reads, src_block_stride, dst_block_stride);
+	return LIZEC_OK;
+}
+
+/* The verified read on the host: lizec_crc32 over the source blocks that
+ * the read consumes, by the rule of csrc/read_verify.h, then the read. */
+extern "C" int lizec_chunk_read_verified_host(
+    int srcs, int rows, const uint8_t *gftbls, int ntables,
+    const uint32_t *tbl_index, const uint64_t *src_ptrs,
+    const uint32_t *src_nblocks, int view_parts, const uint8_t *col_map,
+    const uint32_t *first_block, const uint32_t *block_count,
+    const uint64_t *dst_ptrs, int num_reads, uint32_t src_block_stride,
+    uint32_t dst_block_stride, const uint64_t *crc_ptrs,
+    uint32_t crc_block_stride, uint32_t *bad_out) {
+	if (!crc_ptrs || !bad_out || crc_block_stride < 4) return LIZEC_EINVAL;
+	int64_t entries = lizec_impl_chunk_read_check(
+	    srcs, rows, gftbls, ntables, tbl_index, src_ptrs, src_nblocks,
+	    view_parts, col_map, first_block, block_count, dst_ptrs, num_reads,
+	    src_block_stride, dst_block_stride, nullptr, nullptr);
+	if (entries < 0) return (int)entries;
+	const uint32_t ks = (uint32_t)view_parts;
+	for (int i = 0; i < num_reads; ++i) {
+		const uint64_t *sp = src_ptrs + (size_t)i * srcs;
+		const uint64_t *cp = crc_ptrs + (size_t)i * srcs;
+		const uint32_t *sn = src_nblocks + (size_t)i * srcs;
+		const uint8_t *cm = col_map + (size_t)i * ks;
+		const uint32_t first = first_block[i], end = first + block_count[i];
+		uint32_t bad = 0;
+		for (uint32_t b = first / ks; b <= (end - 1) / ks; ++b) {
+			const uint32_t c0 = b * ks;
+			const uint32_t lo = first > c0 ? first - c0 : 0;
+			const uint32_t hi = end - c0 < ks ? end - c0 : ks;
+			/* the slots whose column is requested; every present slot if a
+			 * lost column is */
+			uint32_t slots = 0;
+			for (uint32_t c = lo; c < hi; ++c) {
+				if (cm[c] >= 0x80) slots = 0xFFFFFFFFu;
+				else slots |= 1u << cm[c];
+			}
+			for (int j = 0; j < srcs; ++j) {
+				if (!((slots >> j) & 1) || !cp[j] || b >= sn[j]) continue;
+				const uint8_t *q = (const uint8_t *)(uintptr_t)cp[j] +
+				                   (uint64_t)b * crc_block_stride;
+				const uint32_t want = ((uint32_t)q[0] << 24) |
+				                      ((uint32_t)q[1] << 16) |
+				                      ((uint32_t)q[2] << 8) | q[3];
+				if (lizec_crc32(0, (const uint8_t *)(uintptr_t)sp[j] +
+				                       (uint64_t)b * src_block_stride,
+				                65536) != want)
+					bad |= 1u << j;
+			}
+		}
+		bad_out[i] = bad;
+	}
+	chunk_read_host_run(srcs, rows, gftbls, tbl_index, src_ptrs, src_nblocks,
+	                    view_parts, col_map, first_block, block_count, dst_ptrs,
+	                    num_reads, src_block_stride, dst_block_stride);
 	return LIZEC_OK;
 }
 

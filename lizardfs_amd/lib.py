@@ -178,6 +178,12 @@ def lib():
         [ctypes.c_void_p]
     L.lizec_chunk_read_host.restype = ctypes.c_int
     L.lizec_chunk_read_host.argtypes = read_args
+    verify_args = [u64p, ctypes.c_uint32, ctypes.c_void_p]
+    L.lizec_chunk_read_verified_batch.restype = ctypes.c_int
+    L.lizec_chunk_read_verified_batch.argtypes = [ctypes.c_void_p] + \
+        read_args + verify_args + [ctypes.c_void_p]
+    L.lizec_chunk_read_verified_host.restype = ctypes.c_int
+    L.lizec_chunk_read_verified_host.argtypes = read_args + verify_args
     write_args = [
         ctypes.c_int, u8p, ctypes.c_void_p, ctypes.c_int, u64p, u32p,
         ctypes.c_int, ctypes.c_uint32, u64p]
