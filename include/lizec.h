@@ -569,9 +569,9 @@ typedef struct lizec_chunk_write {   /* 40 bytes, no padding */
  * range.  A parity output must not overlap a data range, a fill range or
  * another output of the call, and two writes that touch the same row do not
  * belong in one call (canStartOperation, :345-355).  An operation with a hole
- * inside a row is passed as its covering range.  A degraded slice is out of
- * scope: rebuild a lost data part that a fill needs with
- * lizec_chunk_read_batch first.
+ * inside a row is passed as its covering range.  Every fill column must be
+ * readable; a slice with lost parts is written through
+ * lizec_chunk_write_degraded_batch below.
  * Returns LIZEC_EINVAL from the host, with nothing enqueued and no byte
  * written, for a NULL array; num_writes < 1; rows or view_parts outside
  * 1..32; from >= to or to > 65536; block_count == 0 or first_block +
@@ -599,6 +599,98 @@ int lizec_chunk_write_host(int rows, const uint8_t *gftbls,
                            const uint32_t *fill_nblocks, int view_parts,
                            uint32_t fill_block_stride,
                            const uint64_t *par_ptrs);
+
+/* The CLIENT WRITE into a slice with lost parts.  ChunkWriter::fillStripe
+ * (mount/chunk_writer.cc:440-466) fills a partly written row through
+ * readBlocks (:557-615), a planned read over whichever parts have a
+ * location, so a lost data part is rebuilt from the survivors before the
+ * parity is computed.  Rebuild and encode are both linear over GF(2^8): they
+ * fold into one coefficient table over "new columns + old sources", and one
+ * pass reads every needed byte range once and nothing outside [from, to).
+ *
+ * lizec_degraded_write_table builds that table for one row shape of ec(k,m),
+ * or of a xor slice of k data parts (is_xor != 0, m = 1: an all-ones
+ * generator; parts are numbered as ec's here, data 0..k-1, the parity k).
+ *  new_mask  : the data columns that are NEW in the row
+ *  have_mask : the data columns whose part has this block row (not ABSENT)
+ *  avail_mask: the parts, data and parity, that can be read as they are now
+ *  slot_part : [srcs], the part behind each old-source slot, each part at
+ *              most once
+ *  gftbl     : out, 32*(k+srcs)*m bytes, [m][k + srcs][32] in
+ *              gf_vect_mul_init format: column c < k multiplies new column
+ *              c, column k + j the old bytes of slot j
+ *  use_mask  : out, the slots whose column is not all zero
+ * A column of have & ~new whose part is available is a plain fill with
+ * coefficient G[r,c].  One that is not is rebuilt from the first k available
+ * parts, ascending (ec_read_plan.h:126-133; for xor, all the others), by the
+ * inversion lizec_rs_tables uses, and the products G[r,c] * R[c,s] are
+ * folded into the survivors' columns: the table gives, bit for bit, what
+ * rebuilding first and encoding second gives.  A surviving data part outside
+ * have_mask counts as zeros: it is not used and needs no slot.  A row without
+ * a lost fill
+ * column comes out as the healthy table, use_mask exactly its fill columns.
+ * For a xor slice the coefficients cancel (1 ^ 1 = 0) to the
+ * read-modify-write form new ^ old ^ old parity, and the cancelled slots
+ * are not in use_mask.
+ * Returns LIZEC_EINVAL for k, m outside 1..32, srcs outside 1..32, a NULL
+ * array, is_xor with m != 1, a mask bit outside the slice, a slot naming a
+ * part outside the slice or one named before, a part that is needed (a
+ * readable fill column; a survivor that is a parity part or lies in
+ * have_mask) without a slot, and a lost fill column with fewer than k parts available ("Not
+ * enough chunkservers to read full data"); LIZEC_ESINGULAR as
+ * lizec_rs_tables. */
+int lizec_degraded_write_table(int k, int m, int is_xor, uint32_t new_mask,
+                               uint32_t have_mask, uint64_t avail_mask,
+                               const uint8_t *slot_part, int srcs,
+                               uint8_t *gftbl, uint32_t *use_mask);
+
+/* lizec_chunk_write_batch over such tables.  The writes, par_dptrs (0 = not
+ * wanted: how a lost parity part is expressed), par_stride, the CRC slots
+ * and their order, the passes, the scratch and the stream and thread
+ * contract are lizec_chunk_write_batch's.  Instead of fill columns there are
+ *  srcs (1..32) old-source slots: old_dptrs[w][j], old_nblocks[w][j], by the
+ *      ragged call's rules; a slot is a part, data or parity.  Slot j is
+ *      present in row b iff b < old_nblocks[w][j], and is then read at old +
+ *      b*old_block_stride + from, size bytes, any alignment;
+ *  gftbls: ntables tables of 32*(view_parts+srcs)*rows bytes each,
+ *      [row][view_parts + srcs][32]; use_masks[ntables] their slot masks;
+ *  tbl_index[w][3]: the table of the write's first touched row, of the rows
+ *      between (all NEW; its mask should be 0, but the call just obeys the
+ *      mask) and of its last touched row where that is not the first.
+ * Parity r of row b is the XOR of tbl[r][c] * new_c over the columns NEW in
+ * the row and of tbl[r][view_parts + j] * old_j over the slots that are in
+ * the table's mask and present.  A slot outside the mask, or at or past its
+ * count, is neither loaded nor addressed.
+ * An output must not overlap a data range, an old-source range or another
+ * output of the call.  In particular a parity part that serves as an old
+ * source cannot be written in place by the same call (the unaligned load
+ * forms read neighbouring lanes' dwords, so an update in place would race):
+ * stage that parity as packets (par_stride = size) and apply them behind
+ * the call.
+ * Returns LIZEC_EINVAL from the host, with nothing enqueued and no byte
+ * written, for everything lizec_chunk_write_batch refuses (read "old" for
+ * "fill"), and for srcs outside 1..32; ntables < 1; a table index >=
+ * ntables; a mask bit >= srcs; a nonzero count with address 0 on a slot
+ * that is in the mask of a table of a row the write touches.  Where the
+ * healthy call speaks of fill addresses, for the refusal as for the aligned
+ * form, read: the addresses of those slots; a slot outside those masks is
+ * never addressed, whatever it holds. */
+int lizec_chunk_write_degraded_batch(
+    lizec_engine *e, int rows, const uint8_t *gftbls, int ntables,
+    const uint32_t *use_masks, const uint32_t *tbl_index,
+    const lizec_chunk_write *writes, int num_writes,
+    const uint64_t *old_dptrs, const uint32_t *old_nblocks, int srcs,
+    int view_parts, uint32_t old_block_stride, const uint64_t *par_dptrs,
+    void *stream);
+
+/* The same on the host: HOST addresses, no GPU, ec_encode_data per row over
+ * the view_parts + srcs candidates.  Same refusals (nothing written), same
+ * bytes. */
+int lizec_chunk_write_degraded_host(
+    int rows, const uint8_t *gftbls, int ntables, const uint32_t *use_masks,
+    const uint32_t *tbl_index, const lizec_chunk_write *writes, int num_writes,
+    const uint64_t *old_ptrs, const uint32_t *old_nblocks, int srcs,
+    int view_parts, uint32_t old_block_stride, const uint64_t *par_ptrs);
 
 /* Per-block CRC32 over a contiguous device buffer:
  *  dev_crcs_out[b] = lizec_crc32(seed, dev_buf + b*block_len, block_len)

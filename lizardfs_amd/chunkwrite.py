@@ -12,6 +12,15 @@ only (computeParityBlock, :365-402).  Every new data block and every parity
 block leaves as a packet with the CRC of its bytes
 (WriteExecutor::addDataPacket, write_executor.cc:91-107): exactly what
 writegate checks on the other end.
+
+A slice with lost parts is written through write_chunks_degraded, in one
+lizec_chunk_write_degraded_batch call.  fillStripe reads a partly written
+row through readBlocks (:557-615), a planned read over the parts that have
+a location, so a fill column whose part is lost is rebuilt from the
+survivors first.  Here rebuild and encode fold into one coefficient table
+per row shape (lizec_degraded_write_table) over "new columns + old
+sources", and the parity pass reads every needed byte range once; a lost
+part gets no packets, neither data nor parity.
 """
 import collections
 import ctypes
@@ -24,7 +33,7 @@ from . import slice_traits as st
 from .convert import _check_slice, _part_blocks, view_columns
 
 _BLOCK = st.BLOCK_SIZE
-NEW, FILL, ABSENT = "new", "fill", "absent"
+NEW, FILL, ABSENT, LOST = "new", "fill", "absent", "lost"
 
 # lizec_chunk_write: 40 bytes, no padding
 WRITE_DTYPE = np.dtype([("data", "<u8"), ("crcs", "<u8"),
@@ -92,6 +101,50 @@ def plan_write(slice_type, chunk_blocks, first_block, block_count):
     return WritePlan(rows, sorted(read), packets)
 
 
+def _available(slice_type, available_parts, what):
+    n = len(view_columns(slice_type)) + st.parity_parts(slice_type)
+    have = sorted({int(p) for p in available_parts})
+    if have and not 0 <= have[0] <= have[-1] < n:
+        raise ValueError(f"{what}: available part outside slice "
+                         f"{slice_type}")
+    return have
+
+
+def plan_write_degraded(slice_type, available_parts, chunk_blocks,
+                        first_block, block_count):
+    """plan_write for a slice of which only available_parts can be reached,
+    or None if the write cannot be made.  Pure Python.
+
+    rows carry a fourth kind, LOST: a fill column whose part is not
+    available.  It is rebuilt, as ChunkWriter::readBlocks
+    (chunk_writer.cc:557-615) does through the read planner, from the first
+    k available parts in ascending order (ec_read_plan.h:126-133), for a
+    xor slice from all the others; with fewer than k parts available the
+    result is None ("Not enough chunkservers to read full data").
+    read_parts are the old sources: the available fill parts, and for a row
+    with a LOST column those k parts, bar data parts that do not reach the
+    row (zeros).  packets holds the packets of available parts only: a lost
+    part has no WriteExecutor, so neither its data packets nor its parity
+    appear."""
+    plan = plan_write(slice_type, chunk_blocks, first_block, block_count)
+    have = _available(slice_type, available_parts, "plan_write_degraded")
+    cols = view_columns(slice_type)
+    ks = len(cols)
+    blocks = {p: _part_blocks(slice_type, p, chunk_blocks) for p in have}
+    rows, read = [], set()
+    for b, kinds in plan.rows:
+        kinds = [LOST if kind == FILL and cols[c] not in have else kind
+                 for c, kind in enumerate(kinds)]
+        rows.append((b, kinds))
+        read.update(cols[c] for c, kind in enumerate(kinds) if kind == FILL)
+        if LOST in kinds:
+            if len(have) < ks:
+                return None
+            read.update(p for p in have[:ks] if b < blocks[p])
+    packets = [(p, b) for p, b in plan.packets if p in have]
+    return WritePlan(rows, sorted(read), packets)
+
+
 def encode_table(slice_type):
     """The [rows][columns][32] table of a slice's parities: the encode table
     of ec(k,m), all ones for a xor slice (chunk_writer.cc:373-381)."""
@@ -124,9 +177,10 @@ class _Batch:
 
 
 def _prepare(slice_type, fragments, geom, chunk_blocks, data, first_block,
-             block_count, offset, size, fmt, want_parity):
+             block_count, offset, size, fmt, want_parity, available=None):
     """geom(buffer, what, dims) -> (shape, strides, address), or ValueError.
-    Touches neither the library nor a GPU."""
+    Touches neither the library nor a GPU.  available: None, or the
+    available parts of every chunk (the degraded call)."""
     _check_slice(slice_type, "slice_type")
     m = st.parity_parts(slice_type)
     if m < 1:
@@ -168,17 +222,37 @@ def _prepare(slice_type, fragments, geom, chunk_blocks, data, first_block,
     if len(fragments) != ks + m:
         raise ValueError(f"need {ks + m} fragment slots for slice type "
                          f"{slice_type}")
-    plans = [plan_write(slice_type, int(cb[s]), int(first[s]), int(count[s]))
-             for s in range(S)]
+    if available is None:
+        plans = [plan_write(slice_type, int(cb[s]), int(first[s]),
+                            int(count[s])) for s in range(S)]
+    else:
+        plans = [plan_write_degraded(slice_type, available[s], int(cb[s]),
+                                     int(first[s]), int(count[s]))
+                 for s in range(S)]
+        for s, plan in enumerate(plans):
+            if plan is None:
+                raise ValueError(f"chunk {s}: a fill column is lost and "
+                                 f"fewer than {ks} parts are available")
     b = _Batch()
     b.S, b.ks, b.m, b.want, b.plans = S, ks, m, want, plans
+    pars = _parity_parts(slice_type)
+    b.wants = [want if available is None else
+               [r for r in want if pars[r] in available[s]]
+               for s in range(S)]
     b.slice_type, b.offset, b.size = slice_type, offset, size
     b.touched = np.array([len(p.rows) for p in plans], np.int64)
     b.count = count
-    b.fill = np.zeros((S, ks), np.uint64)
-    b.fill_nb = np.zeros((S, ks), np.uint32)
-    b.fill_stride = bstride
     need = sorted({p for plan in plans for p in plan.read_parts})
+    # the healthy call has a slot per view column, the degraded call a slot
+    # per part that any write reads
+    b.slots = list(cols) if available is None else (need or [cols[0]])
+    if len(b.slots) > 32:
+        raise ValueError(f"the writes read {len(b.slots)} parts; one call "
+                         f"takes 32")
+    b.fill = np.zeros((S, len(b.slots)), np.uint64)
+    b.fill_nb = np.zeros((S, len(b.slots)), np.uint32)
+    b.fill_stride = bstride
+    b.first, b.chunk_blocks, b.available = first, cb, available
     for p in need:
         if fragments[p] is None:
             raise ValueError(f"fragment {p} is needed to fill the rows the "
@@ -187,7 +261,7 @@ def _prepare(slice_type, fragments, geom, chunk_blocks, data, first_block,
         if fshape[0] != S or fstrides[1] != 1:
             raise ValueError(f"fragment {p} must be [S={S}, L] with "
                              f"contiguous rows")
-        c = cols.index(p)
+        c = b.slots.index(p)
         for s in range(S):
             if p not in plans[s].read_parts:
                 continue
@@ -247,7 +321,7 @@ def _packets(b, data, parity, crcs):
                                  int(crcs[s, i]), data[s, i]))
             else:
                 r = pars.index(part)
-                if r not in b.want:
+                if r not in b.wants[s]:
                     continue
                 pk.append(Packet(part, blk, b.offset, b.size,
                                  int(crcs[s, n + (blk - r0) * b.m + r]),
@@ -335,4 +409,170 @@ def write_chunks_host(slice_type, fragments, chunk_blocks, data, first_block,
     L.check(_call(L.lib().lizec_chunk_write_host, (), b, parity.ctypes.data,
                   parity.strides[0], crcs.ctypes.data, crcs.strides[0], ()),
             "lizec_chunk_write_host")
+    return parity, crcs, _packets(b, data, parity, crcs)
+
+
+def _builder_part(slice_type, part):
+    """A slice part in lizec_degraded_write_table's numbering: the data
+    parts in column order, then the parity parts."""
+    cols = view_columns(slice_type)
+    if part in cols:
+        return cols.index(part)
+    return len(cols) + _parity_parts(slice_type).index(part)
+
+
+def _degraded_tables(b):
+    """The tables of a degraded batch, one per distinct (row shape,
+    availability): (tables [n, m*(ks+srcs)*32], masks [n], index [S, 3])."""
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    t, ks, m, srcs = b.slice_type, b.ks, b.m, len(b.slots)
+    cols = view_columns(t)
+    slot_part = np.array([_builder_part(t, p) for p in b.slots], np.uint8)
+    keys, tables, masks = {}, [], []
+    index = np.zeros((b.S, 3), np.uint32)
+    for s, plan in enumerate(b.plans):
+        avail = sum(1 << _builder_part(t, p)
+                    for p in _available(t, b.available[s], "available_parts"))
+        nb = [_part_blocks(t, p, int(b.chunk_blocks[s])) for p in cols]
+        shapes = [plan.rows[0], plan.rows[len(plan.rows) // 2],
+                  plan.rows[-1]]
+        for i, (row, kinds) in enumerate(shapes):
+            new = sum(1 << c for c in range(ks) if kinds[c] == NEW)
+            have = sum(1 << c for c in range(ks) if row < nb[c])
+            key = (new, have, avail)
+            if key not in keys:
+                tbl = np.zeros(32 * (ks + srcs) * m, np.uint8)
+                mask = ctypes.c_uint32()
+                rc = L.lib().lizec_degraded_write_table(
+                    ks, m, int(st.is_xor(t)), new, have, avail,
+                    slot_part.ctypes.data_as(u8p), srcs,
+                    tbl.ctypes.data_as(u8p), ctypes.byref(mask))
+                if rc != 0:
+                    # plan_write_degraded has found the chunk writable, so
+                    # EINVAL here is a part the row needs without a slot
+                    why = {-2: f"a part the row needs is not among the "
+                               f"slots {b.slots} (plan and builder "
+                               f"disagree)",
+                           -1: "the surviving parts' matrix is singular"}
+                    raise ValueError(
+                        f"chunk {s}, row {row}: lizec_degraded_write_table "
+                        f"{L._ERRNAMES.get(rc, rc)}: {why.get(rc, 'refused')}"
+                        f"; new columns {new:#x}, columns with the row "
+                        f"{have:#x}, available parts {avail:#x}")
+                keys[key] = len(tables)
+                tables.append(tbl)
+                masks.append(mask.value)
+            index[s, i] = keys[key]
+    return np.stack(tables), np.array(masks, np.uint32), index
+
+
+def _call_degraded(fn, head, b, tables, par_addr, par_row_stride, crc_addr,
+                   crc_row_stride, tail):
+    """_call for the degraded entry points."""
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    tbls, masks, index = tables
+    rows = np.arange(b.S, dtype=np.uint64)
+    par = np.zeros((b.S, b.m), np.uint64)
+    for s in range(b.S):
+        for r in b.wants[s]:
+            par[s, r] = par_addr + s * par_row_stride + r * b.size
+    b.writes["crcs"] = np.uint64(crc_addr) + rows * np.uint64(crc_row_stride)
+    return fn(*head, b.m, tbls.ctypes.data_as(u8p), len(masks),
+              masks.ctypes.data_as(u32p), index.ctypes.data_as(u32p),
+              ctypes.c_void_p(b.writes.ctypes.data), b.S,
+              b.fill.ctypes.data_as(u64p), b.fill_nb.ctypes.data_as(u32p),
+              len(b.slots), b.ks, b.fill_stride, par.ctypes.data_as(u64p),
+              *tail)
+
+
+def _per_chunk_available(slice_type, available_parts, chunk_blocks):
+    S = len(np.asarray(chunk_blocks).reshape(-1))
+    av = list(available_parts)
+    if all(isinstance(p, (int, np.integer)) for p in av):
+        av = [av] * S
+    if len(av) != S:
+        raise ValueError(f"available_parts has {len(av)} entries for {S} "
+                         f"chunks")
+    _check_slice(slice_type, "slice_type")
+    return [frozenset(_available(slice_type, a, "available_parts"))
+            for a in av]
+
+
+def write_chunks_degraded(slice_type, fragments, chunk_blocks, data,
+                          first_block, block_count, available_parts,
+                          offset=0, size=_BLOCK, fmt=None, want_parity=None):
+    """write_chunks into chunks of which only available_parts (one set for
+    the batch, or one per chunk) can be reached, in one
+    lizec_chunk_write_degraded_batch call.
+
+    fragments: as for write_chunks; the slots of the parts that a write
+      reads (plan_write_degraded(...).read_parts: data parts and parity
+      parts, as they are now) hold [S, L] CUDA uint8 row views.
+    want_parity is intersected with every chunk's availability: a lost
+      parity part is not computed and gets no packet, as a lost data part
+      gets none for its new blocks.
+    The parity comes back staged, never in place, so a parity part that is
+    read as an old source is not overwritten by the call.
+    Returns (parity, crcs, packets) like write_chunks.  Raises ValueError,
+    before any GPU use, for what the library would refuse and for a chunk
+    that cannot be written (a lost fill column with fewer than k parts
+    available)."""
+    import torch
+
+    def geom(t, what, dims):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or \
+                not t.is_cuda or t.dim() != dims:
+            raise ValueError(f"{what} must be a CUDA uint8 tensor of "
+                             f"{dims} dimensions")
+        if isinstance(data, torch.Tensor) and t.device != data.device:
+            raise ValueError(f"{what} lies on {t.device}, data on "
+                             f"{data.device}")
+        return tuple(t.shape), tuple(t.stride()), t.data_ptr()
+
+    avail = _per_chunk_available(slice_type, available_parts, chunk_blocks)
+    b = _prepare(slice_type, fragments, geom, chunk_blocks, data, first_block,
+                 block_count, offset, size, fmt, want_parity, avail)
+    tables = _degraded_tables(b)
+    device = data.device.index
+    parity = torch.zeros((b.S, b.T, b.m, size), dtype=torch.uint8,
+                         device=data.device)
+    crcs = torch.zeros((b.S, b.ncrc), dtype=torch.int32, device=data.device)
+    stream = torch.cuda.current_stream(device)
+    L.check(_call_degraded(L.lib().lizec_chunk_write_degraded_batch,
+                           (L.engine(device),), b, tables, parity.data_ptr(),
+                           parity.stride(0), crcs.data_ptr(),
+                           4 * crcs.stride(0),
+                           (ctypes.c_void_p(stream.cuda_stream),)),
+            "lizec_chunk_write_degraded_batch")
+    stream.synchronize()
+    host = crcs.cpu().numpy().view(np.uint32)
+    return parity, crcs, _packets(b, data, parity, host)
+
+
+def write_chunks_degraded_host(slice_type, fragments, chunk_blocks, data,
+                               first_block, block_count, available_parts,
+                               offset=0, size=_BLOCK, fmt=None,
+                               want_parity=None):
+    """write_chunks_degraded over numpy arrays, through
+    lizec_chunk_write_degraded_host: no GPU is needed.  crcs comes back as
+    uint32."""
+    def geom(a, what, dims):
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or \
+                a.ndim != dims:
+            raise ValueError(f"{what} must be a uint8 array of {dims} "
+                             f"dimensions")
+        return a.shape, a.strides, a.ctypes.data
+
+    avail = _per_chunk_available(slice_type, available_parts, chunk_blocks)
+    b = _prepare(slice_type, fragments, geom, chunk_blocks, data, first_block,
+                 block_count, offset, size, fmt, want_parity, avail)
+    tables = _degraded_tables(b)
+    parity = np.zeros((b.S, b.T, b.m, size), np.uint8)
+    crcs = np.zeros((b.S, b.ncrc), np.uint32)
+    L.check(_call_degraded(L.lib().lizec_chunk_write_degraded_host, (), b,
+                           tables, parity.ctypes.data, parity.strides[0],
+                           crcs.ctypes.data, crcs.strides[0], ()),
+            "lizec_chunk_write_degraded_host")
     return parity, crcs, _packets(b, data, parity, crcs)

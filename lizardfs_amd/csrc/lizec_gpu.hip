@@ -49,6 +49,7 @@
 #include "read_gate.h"
 #include "read_verify.h"
 #include "ec_kernel_write.h"
+#include "ec_kernel_write_degraded.h"
 
 /* Product kernel configuration (chosen by the variant A/B harness,
  * bench_variants.hip; numbers in profiles/ROUND1.md + ROUND2.md):
@@ -2168,6 +2169,198 @@ extern "C" int lizec_chunk_write_batch(
 		                   dim3((n + kCrcRangesThreads - 1) / kCrcRangesThreads),
 		                   dim3(kCrcRangesThreads), 0, s, d_crcs,
 		                   c->d_ptrs + nfill + npar + ncrc, n);
+		LIZEC_CHECK(hipGetLastError());
+	}
+	return LIZEC_OK;
+}
+
+/* ------------------------------------------------------------------ */
+/* Degraded chunk writes: the same, with lost fill columns rebuilt in  */
+/* the parity pass (ec_kernel_write_degraded.h)                        */
+/* ------------------------------------------------------------------ */
+
+struct write_degraded_dev {
+	const uint8_t *tbls;
+	const uint32_t *masks, *index;
+	const uint4 *map16, *map8;   /* tile maps for 16 KiB / 8 KiB tiles */
+	uint32_t tiles16, tiles8;
+	const lizec_chunk_write *writes;
+	const uint64_t *old, *par;
+	const uint32_t *old_nb;
+};
+
+/* One pass of the degraded write kernel, as launch_chunk_write. */
+template <int D>
+static void launch_chunk_write_degraded(int ks, int srcs, int dest_base,
+                                        int rows, const write_degraded_dev &w,
+                                        uint32_t old_stride, bool fast,
+                                        hipStream_t s) {
+	constexpr int CH = ec_chunks_for(D);
+	const uint32_t total_tiles = CH == 4 ? w.tiles16 : w.tiles8;
+	const uint4 *map = CH == 4 ? w.map16 : w.map8;
+	size_t lds = (size_t)D * (ks + srcs) * kECTblBytes;
+#define LIZEC_LAUNCH_WRITE_DEG(FAST)                                        \
+	hipLaunchKernelGGL(                                                     \
+	    HIP_KERNEL_NAME(ec_chunk_write_degraded_kernel<D, CH, FAST>),       \
+	    dim3(total_tiles), dim3(kThreads), lds, s, ks, srcs, dest_base,     \
+	    rows, w.tbls, w.masks, w.index, map, w.writes, w.old, w.old_nb,     \
+	    w.par, old_stride)
+	if (fast) LIZEC_LAUNCH_WRITE_DEG(true);
+	else LIZEC_LAUNCH_WRITE_DEG(false);
+#undef LIZEC_LAUNCH_WRITE_DEG
+}
+
+extern "C" int64_t lizec_impl_chunk_write_degraded_check(
+    int rows, const uint8_t *gftbls, int ntables, const uint32_t *use_masks,
+    const uint32_t *tbl_index, const lizec_chunk_write *writes, int num_writes,
+    const uint64_t *old_ptrs, const uint32_t *old_nblocks, int srcs,
+    int view_parts, uint32_t old_block_stride, const uint64_t *par_ptrs,
+    uint64_t *bits_out, uint64_t *tiles16_out, uint64_t *tiles8_out,
+    uint64_t *ncrc_out);
+
+extern "C" int lizec_chunk_write_degraded_batch(
+    lizec_engine *e, int rows, const uint8_t *gftbls, int ntables,
+    const uint32_t *use_masks, const uint32_t *tbl_index,
+    const lizec_chunk_write *writes, int num_writes,
+    const uint64_t *old_dptrs, const uint32_t *old_nblocks, int srcs,
+    int view_parts, uint32_t old_block_stride, const uint64_t *par_dptrs,
+    void *stream) {
+	if (!e) return LIZEC_EINVAL;
+	uint64_t bits, tiles16, tiles8, ncrc;
+	int64_t entries = lizec_impl_chunk_write_degraded_check(
+	    rows, gftbls, ntables, use_masks, tbl_index, writes, num_writes,
+	    old_dptrs, old_nblocks, srcs, view_parts, old_block_stride, par_dptrs,
+	    &bits, &tiles16, &tiles8, &ncrc);
+	if (entries <= 0) return LIZEC_EINVAL;
+	const bool fast = (bits & 15) == 0;
+	hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+	LIZEC_CHECK(hipSetDevice(e->device));
+
+	/* lizec_chunk_write_batch's scratch, with the tables' masks and the
+	 * writes' table indices behind the tables */
+	const int last = rows % 8 ? rows % 8 : 8;
+	const bool use16 = last <= 4, use8 = rows > 8 || last > 4;
+	auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+	const size_t W = (size_t)num_writes, ks = (size_t)view_parts;
+	const size_t nold = W * srcs, npar = W * rows;
+	size_t ntbl = (size_t)ntables * rows * (ks + srcs);   /* 32 B each */
+	size_t o_mask = up16(ntbl * kECTblBytes);
+	size_t o_index = o_mask + up16((size_t)ntables * 4);
+	size_t o_map16 = o_index + up16(W * 3 * 4);
+	size_t o_map8 = o_map16 + (use16 ? (size_t)tiles16 * 16 : 0);
+	size_t o_wr = o_map8 + (use8 ? (size_t)tiles8 * 16 : 0);
+	size_t o_onb = o_wr + up16(W * sizeof(lizec_chunk_write));
+	size_t o_len = o_onb + up16(nold * 4);
+	size_t bytes = o_len + up16((size_t)ncrc * 4);
+	const size_t slots = nold + npar + 2 * (size_t)ncrc;
+	lizec_stream_ctx *c;
+	int r = ctx_acquire_ragged(e, s, slots + ((size_t)ncrc + 1) / 2, slots * 8,
+	                           bytes, &c);
+	if (r != LIZEC_OK) return r;
+	uint8_t *h = c->h_ragged;
+	for (size_t i = 0; i < ntbl; ++i)
+		pack_mixed_radix(gftbls + i * 32, h + i * kECTblBytes);
+	memcpy(h + o_mask, use_masks, (size_t)ntables * 4);
+	memcpy(h + o_index, tbl_index, W * 3 * 4);
+	memcpy(h + o_wr, writes, W * sizeof(lizec_chunk_write));
+	memcpy(h + o_onb, old_nblocks, nold * 4);
+	uint64_t *pstage = (uint64_t *)(c->h_staging + (size_t)kECTblBytes * 32 * 32);
+	memcpy(pstage, old_dptrs, nold * 8);
+	memcpy(pstage + nold, par_dptrs, npar * 8);
+	uint32_t *m16 = (uint32_t *)(h + o_map16), *m8 = (uint32_t *)(h + o_map8);
+	uint32_t *lens = (uint32_t *)(h + o_len);
+	uint64_t *addrs = pstage + nold + npar, *outs = addrs + ncrc;
+	size_t nr = 0;
+	for (size_t i = 0; i < W; ++i) {
+		const lizec_chunk_write &w = writes[i];
+		const uint32_t size = w.to - w.from;
+		const uint32_t r0 = w.first_block / (uint32_t)ks;
+		const uint32_t r1 = (w.first_block + w.block_count - 1) / (uint32_t)ks;
+		const uint64_t *pp = par_dptrs + i * rows;
+		if (w.crcs)
+			for (uint32_t b = 0; b < w.block_count; ++b) {
+				addrs[nr] = w.data + (b ? (uint64_t)b * w.data_stride : 0);
+				lens[nr] = size;
+				outs[nr++] = w.crcs + 4ull * b;
+			}
+		for (uint32_t b = r0; b <= r1; ++b) {
+			if (use16)
+				for (uint32_t t = 0; t * 16384u < size; ++t) {
+					*m16++ = (uint32_t)i;
+					*m16++ = b;
+					*m16++ = t;
+					*m16++ = b - r0;
+				}
+			if (use8)
+				for (uint32_t t = 0; t * 8192u < size; ++t) {
+					*m8++ = (uint32_t)i;
+					*m8++ = b;
+					*m8++ = t;
+					*m8++ = b - r0;
+				}
+			if (!w.crcs) continue;
+			for (int l = 0; l < rows; ++l) {
+				if (!pp[l]) continue;
+				addrs[nr] =
+				    pp[l] + (b > r0 ? (uint64_t)(b - r0) * w.par_stride : 0);
+				lens[nr] = size;
+				outs[nr++] = w.crcs + 4ull * (w.block_count +
+				                              (uint64_t)(b - r0) * rows + l);
+			}
+		}
+	}
+	(void)nr;   /* == ncrc: the check function counted the same ranges */
+	LIZEC_CHECK(hipMemcpyAsync(c->d_ragged, h, bytes, hipMemcpyHostToDevice, s));
+	LIZEC_CHECK(hipMemcpyAsync(c->d_ptrs, pstage, slots * 8,
+	                           hipMemcpyHostToDevice, s));
+	LIZEC_CHECK(hipEventRecord(c->uploaded, s));
+	c->ev_recorded = true;
+
+	write_degraded_dev wd;
+	wd.tbls = c->d_ragged;
+	wd.masks = (const uint32_t *)(c->d_ragged + o_mask);
+	wd.index = (const uint32_t *)(c->d_ragged + o_index);
+	wd.map16 = (const uint4 *)(c->d_ragged + o_map16);
+	wd.map8 = (const uint4 *)(c->d_ragged + o_map8);
+	wd.tiles16 = (uint32_t)tiles16;
+	wd.tiles8 = (uint32_t)tiles8;
+	wd.writes = (const lizec_chunk_write *)(c->d_ragged + o_wr);
+	wd.old_nb = (const uint32_t *)(c->d_ragged + o_onb);
+	wd.old = c->d_ptrs;
+	wd.par = c->d_ptrs + nold;
+	for (int base = 0; base < rows;) {
+		int d = rows - base;
+		if (d > 8) d = 8;
+#define LIZEC_LAUNCH_WRITE_DEG_D(D)                                         \
+	launch_chunk_write_degraded<D>(view_parts, srcs, base, rows, wd,        \
+	                               old_block_stride, fast, s)
+		switch (d) {
+		case 1: LIZEC_LAUNCH_WRITE_DEG_D(1); break;
+		case 2: LIZEC_LAUNCH_WRITE_DEG_D(2); break;
+		case 3: LIZEC_LAUNCH_WRITE_DEG_D(3); break;
+		case 4: LIZEC_LAUNCH_WRITE_DEG_D(4); break;
+		case 5: LIZEC_LAUNCH_WRITE_DEG_D(5); break;
+		case 6: LIZEC_LAUNCH_WRITE_DEG_D(6); break;
+		case 7: LIZEC_LAUNCH_WRITE_DEG_D(7); break;
+		default: LIZEC_LAUNCH_WRITE_DEG_D(8); break;
+		}
+#undef LIZEC_LAUNCH_WRITE_DEG_D
+		base += d;
+	}
+	LIZEC_CHECK(hipGetLastError());
+	if (ncrc) {
+		/* behind the parity passes on the same stream, as in
+		 * lizec_chunk_write_batch */
+		const uint32_t n = (uint32_t)ncrc;
+		uint32_t *d_crcs = (uint32_t *)(c->d_ptrs + nold + npar + 2 * ncrc);
+		r = launch_crc_ranges(e, c->d_ptrs + nold + npar,
+		                      (const uint32_t *)(c->d_ragged + o_len), n, 0u,
+		                      d_crcs, nullptr, s);
+		if (r != LIZEC_OK) return r;
+		hipLaunchKernelGGL(chunk_write_crc_scatter_kernel,
+		                   dim3((n + kCrcRangesThreads - 1) / kCrcRangesThreads),
+		                   dim3(kCrcRangesThreads), 0, s, d_crcs,
+		                   c->d_ptrs + nold + npar + ncrc, n);
 		LIZEC_CHECK(hipGetLastError());
 	}
 	return LIZEC_OK;

@@ -9,6 +9,7 @@
  */
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 #include "../../include/lizec.h"
 
@@ -1007,6 +1008,263 @@ extern "C" int lizec_chunk_write_host(
 			for (int l = 0; l < nw; ++l)
 				out[l] = (uint8_t *)(uintptr_t)pp[want_row[l]] + poff;
 			ec_encode_data((int)size, (int)ks, nw, tbl, in, out);
+			if (crcs)
+				for (int l = 0; l < nw; ++l)
+					crcs[w.block_count + (size_t)(b - r0) * rows + want_row[l]] =
+					    lizec_crc32(0, out[l], size);
+		}
+	}
+	return LIZEC_OK;
+}
+
+/* ------------------------------------------------------------------ */
+/* Degraded chunk write: the composite table, the checks and the host */
+/* twin (pure host)                                                   */
+/* ------------------------------------------------------------------ */
+
+/* One coefficient table over "new columns + old sources" for a row shape of
+ * a slice with lost parts; see lizec.h.  coef[r][c], c < k, is G[r,c] for a
+ * NEW column; coef[r][k + j] collects, for the part behind slot j, G[r,c] if
+ * it is the readable fill column c, and G[r,c] * R[c,s] for every lost fill
+ * column c that is rebuilt from it.  The products are folded before the
+ * tables are expanded, so the table gives what rebuilding first and encoding
+ * second gives, bit for bit. */
+extern "C" int lizec_degraded_write_table(
+    int k, int m, int is_xor, uint32_t new_mask, uint32_t have_mask,
+    uint64_t avail_mask, const uint8_t *slot_part, int srcs, uint8_t *gftbl,
+    uint32_t *use_mask) {
+	if (k < 1 || k > MAXK || m < 1 || m > MAXM || srcs < 1 || srcs > 32)
+		return LIZEC_EINVAL;
+	if (!slot_part || !gftbl || !use_mask) return LIZEC_EINVAL;
+	if (is_xor && m != 1) return LIZEC_EINVAL;
+	const int nparts = k + m;
+	const uint64_t all = nparts == 64 ? ~0ULL : (((uint64_t)1 << nparts) - 1);
+	const uint32_t cols = k == 32 ? ~0u : ((1u << k) - 1);
+	if ((new_mask & ~cols) || (have_mask & ~cols) || (avail_mask & ~all))
+		return LIZEC_EINVAL;
+	int slot_of[MAXP];
+	for (int p = 0; p < nparts; ++p) slot_of[p] = -1;
+	for (int j = 0; j < srcs; ++j) {
+		if (slot_part[j] >= nparts || slot_of[slot_part[j]] >= 0)
+			return LIZEC_EINVAL;
+		slot_of[slot_part[j]] = j;
+	}
+	const uint32_t fill = have_mask & ~new_mask;
+	const uint32_t lost = fill & ~(uint32_t)(avail_mask & cols);
+
+	/* the generator: its parity rows are G */
+	uint8_t rs_matrix[MAXP * MAXK];
+	if (is_xor) {
+		memset(rs_matrix, 0, sizeof rs_matrix);
+		for (int c = 0; c < k; ++c) rs_matrix[c * k + c] = rs_matrix[k * k + c] = 1;
+	} else if (m >= 5 || (m == 4 && k > 20)) {
+		gf_gen_cauchy1_matrix(rs_matrix, nparts, k);
+	} else {
+		gf_gen_rs_matrix(rs_matrix, nparts, k);
+	}
+	const uint8_t *G = rs_matrix + (size_t)k * k;
+
+	/* the rebuild of lost columns: the first k available parts, ascending
+	 * (ec_read_plan.h:126-133); row c of decode_m gives data column c over
+	 * them, by the inversion of lizec_rs_tables */
+	int surv[MAXK];
+	uint8_t decode_m[MAXK * MAXK];
+	if (lost) {
+		int ns = 0;
+		for (int p = 0; p < nparts && ns < k; ++p)
+			if ((avail_mask >> p) & 1) surv[ns++] = p;
+		if (ns < k) return LIZEC_EINVAL;   /* not enough parts to read */
+		uint64_t present = 0;
+		for (int i = 0; i < k; ++i) {
+			/* a data part without this block row is zeros: it needs no slot */
+			const bool zeros = surv[i] < k && !((have_mask >> surv[i]) & 1);
+			if (!zeros && slot_of[surv[i]] < 0) return LIZEC_EINVAL;
+			present |= (uint64_t)1 << surv[i];
+		}
+		uint8_t work[MAXP * MAXK];
+		select_rows(work, rs_matrix, nparts, k, present);
+		if (gf_invert_matrix(work, decode_m, k) != 0) return LIZEC_ESINGULAR;
+	}
+
+	const int nc = k + srcs;
+	uint8_t coef[MAXM * 64];
+	memset(coef, 0, (size_t)m * nc);
+	for (int c = 0; c < k; ++c) {
+		const uint32_t bit = 1u << c;
+		if (new_mask & bit) {
+			for (int r = 0; r < m; ++r) coef[r * nc + c] = G[r * k + c];
+		} else if (lost & bit) {
+			for (int i = 0; i < k; ++i) {
+				if (slot_of[surv[i]] < 0) continue;   /* zeros, see above */
+				const int at = k + slot_of[surv[i]];
+				for (int r = 0; r < m; ++r)
+					coef[r * nc + at] ^=
+					    gfmul(G[r * k + c], decode_m[c * k + i]);
+			}
+		} else if (fill & bit) {
+			if (slot_of[c] < 0) return LIZEC_EINVAL;
+			for (int r = 0; r < m; ++r)
+				coef[r * nc + k + slot_of[c]] ^= G[r * k + c];
+		}
+	}
+	/* a data part without this block row counts as zeros: never read */
+	uint32_t mask = 0;
+	for (int j = 0; j < srcs; ++j) {
+		const int p = slot_part[j];
+		bool used = false;
+		for (int r = 0; r < m; ++r) {
+			if (p < k && !((have_mask >> p) & 1)) coef[r * nc + k + j] = 0;
+			used |= coef[r * nc + k + j] != 0;
+		}
+		if (used) mask |= 1u << j;
+	}
+	ec_init_tables(nc, m, coef, gftbl);
+	*use_mask = mask;
+	return LIZEC_OK;
+}
+
+/* The host checks of the degraded chunk write, shared by
+ * lizec_chunk_write_degraded_host and lizec_chunk_write_degraded_batch
+ * (lizec_gpu.hip); the outputs are those of lizec_impl_chunk_write_check. */
+extern "C" int64_t lizec_impl_chunk_write_degraded_check(
+    int rows, const uint8_t *gftbls, int ntables, const uint32_t *use_masks,
+    const uint32_t *tbl_index, const lizec_chunk_write *writes, int num_writes,
+    const uint64_t *old_ptrs, const uint32_t *old_nblocks, int srcs,
+    int view_parts, uint32_t old_block_stride, const uint64_t *par_ptrs,
+    uint64_t *bits_out, uint64_t *tiles16_out, uint64_t *tiles8_out,
+    uint64_t *ncrc_out) {
+	if (!gftbls || !use_masks || !tbl_index || !writes || !old_ptrs ||
+	    !old_nblocks || !par_ptrs)
+		return LIZEC_EINVAL;
+	if (num_writes < 1 || rows < 1 || rows > 32 || view_parts < 1 ||
+	    view_parts > 32 || srcs < 1 || srcs > 32 || ntables < 1)
+		return LIZEC_EINVAL;
+	if (old_block_stride < 65536u) return LIZEC_EINVAL;
+	if (srcs < 32)
+		for (int t = 0; t < ntables; ++t)
+			if (use_masks[t] >> srcs) return LIZEC_EINVAL;
+	const uint32_t ks = (uint32_t)view_parts;
+	uint64_t bits = 0, entries = 0, tiles16 = 0, tiles8 = 0, ncrc = 0;
+	for (int i = 0; i < num_writes; ++i) {
+		const lizec_chunk_write &w = writes[i];
+		if (w.from >= w.to || w.to > 65536u) return LIZEC_EINVAL;
+		const uint32_t size = w.to - w.from;
+		const uint64_t first = w.first_block, count = w.block_count;
+		if (count == 0 || first + count > 1048576u) return LIZEC_EINVAL;
+		if (!w.data || (w.crcs & 3)) return LIZEC_EINVAL;
+		const uint64_t touched = (first + count - 1) / ks - first / ks + 1;
+		bits |= w.data | size | w.from;
+		if (count > 1) {
+			if (w.data_stride < size) return LIZEC_EINVAL;
+			bits |= w.data_stride;
+		}
+		if (touched > 1) {
+			if (w.par_stride < size) return LIZEC_EINVAL;
+			bits |= w.par_stride;
+		}
+		for (int t = 0; t < 3; ++t)
+			if (tbl_index[(size_t)i * 3 + t] >= (uint32_t)ntables)
+				return LIZEC_EINVAL;
+		const uint64_t *op = old_ptrs + (size_t)i * srcs;
+		const uint32_t *on = old_nblocks + (size_t)i * srcs;
+		/* the slots that a table of a touched row may take; the others are
+		 * never addressed, so neither refused nor part of the aligned form */
+		uint32_t used = use_masks[tbl_index[(size_t)i * 3]];
+		if (touched > 1) used |= use_masks[tbl_index[(size_t)i * 3 + 2]];
+		if (touched > 2) used |= use_masks[tbl_index[(size_t)i * 3 + 1]];
+		for (int j = 0; j < srcs; ++j) {
+			if (on[j] > 32768u) return LIZEC_EINVAL;
+			if (!on[j] || !((used >> j) & 1)) continue;
+			if (!op[j]) return LIZEC_EINVAL;
+			bits |= op[j] | old_block_stride;
+		}
+		uint32_t wanted = 0;
+		for (int r = 0; r < rows; ++r) {
+			const uint64_t p = par_ptrs[(size_t)i * rows + r];
+			if (!p) continue;
+			++wanted;
+			bits |= p;
+		}
+		if (!wanted && !w.crcs) return LIZEC_EINVAL;
+		entries += touched;
+		tiles16 += touched * ((size + 16383u) / 16384u);
+		tiles8 += touched * ((size + 8191u) / 8192u);
+		if (w.crcs) ncrc += count + touched * wanted;
+	}
+	/* the grids the passes launch, as in lizec_impl_chunk_write_check */
+	const int last = rows % 8 ? rows % 8 : 8;
+	const bool use16 = last <= 4, use8 = rows > 8 || last > 4;
+	if ((use16 && tiles16 > 0x7FFFFFFFull) || (use8 && tiles8 > 0x7FFFFFFFull))
+		return LIZEC_EINVAL;
+	if (ncrc > ((uint64_t)1 << 24)) return LIZEC_EINVAL;
+	if (bits_out) *bits_out = bits;
+	if (tiles16_out) *tiles16_out = tiles16;
+	if (tiles8_out) *tiles8_out = tiles8;
+	if (ncrc_out) *ncrc_out = ncrc;
+	return (int64_t)entries;
+}
+
+/* lizec_chunk_write_host with the degraded call's source walk: per touched
+ * row the ks + srcs candidates are pointed at the new data, an old slot that
+ * is in the row's mask and has the block, or a block of zeros, and
+ * ec_encode_data applies the row's table; see lizec.h. */
+extern "C" int lizec_chunk_write_degraded_host(
+    int rows, const uint8_t *gftbls, int ntables, const uint32_t *use_masks,
+    const uint32_t *tbl_index, const lizec_chunk_write *writes, int num_writes,
+    const uint64_t *old_ptrs, const uint32_t *old_nblocks, int srcs,
+    int view_parts, uint32_t old_block_stride, const uint64_t *par_ptrs) {
+	int64_t entries = lizec_impl_chunk_write_degraded_check(
+	    rows, gftbls, ntables, use_masks, tbl_index, writes, num_writes,
+	    old_ptrs, old_nblocks, srcs, view_parts, old_block_stride, par_ptrs,
+	    nullptr, nullptr, nullptr, nullptr);
+	if (entries < 0) return (int)entries;
+	lizec_crc32_init();
+	const uint32_t ks = (uint32_t)view_parts, nc = ks + (uint32_t)srcs;
+	static const uint8_t zeros[65536] = {0};
+	std::vector<uint8_t> tbl((size_t)32 * nc * 32);   /* wanted rows, closed up */
+	for (int i = 0; i < num_writes; ++i) {
+		const lizec_chunk_write &w = writes[i];
+		const uint32_t size = w.to - w.from;
+		const uint32_t first = w.first_block, end = first + w.block_count;
+		const uint64_t *op = old_ptrs + (size_t)i * srcs;
+		const uint32_t *on = old_nblocks + (size_t)i * srcs;
+		const uint64_t *pp = par_ptrs + (size_t)i * rows;
+		const uint8_t *data = (const uint8_t *)(uintptr_t)w.data;
+		const uint64_t dstride = w.block_count > 1 ? w.data_stride : 0;
+		uint32_t *crcs = (uint32_t *)(uintptr_t)w.crcs;
+		int want_row[32], nw = 0;
+		for (int r = 0; r < rows; ++r)
+			if (pp[r]) want_row[nw++] = r;
+		if (crcs)
+			for (uint32_t b = 0; b < w.block_count; ++b)
+				crcs[b] = lizec_crc32(0, data + b * dstride, size);
+		if (!nw) continue;
+		const uint32_t r0 = first / ks, r1 = (end - 1) / ks;
+		for (uint32_t b = r0; b <= r1; ++b) {
+			const uint32_t ti =
+			    tbl_index[(size_t)i * 3 + (b == r0 ? 0 : b == r1 ? 2 : 1)];
+			const uint32_t mask = use_masks[ti];
+			const uint8_t *t = gftbls + (size_t)ti * rows * nc * 32;
+			for (int l = 0; l < nw; ++l)
+				memcpy(tbl.data() + (size_t)l * nc * 32,
+				       t + (size_t)want_row[l] * nc * 32, (size_t)nc * 32);
+			uint8_t *in[64], *out[32];
+			for (uint32_t c = 0; c < ks; ++c) {
+				const uint32_t cb = b * ks + c;
+				in[c] = cb >= first && cb < end
+				            ? (uint8_t *)data + (cb - first) * dstride
+				            : (uint8_t *)zeros;
+			}
+			for (int j = 0; j < srcs; ++j)
+				in[ks + j] = ((mask >> j) & 1) && b < on[j]
+				                 ? (uint8_t *)(uintptr_t)op[j] +
+				                       (uint64_t)b * old_block_stride + w.from
+				                 : (uint8_t *)zeros;
+			const uint64_t poff =
+			    b > r0 ? (uint64_t)(b - r0) * w.par_stride : 0;
+			for (int l = 0; l < nw; ++l)
+				out[l] = (uint8_t *)(uintptr_t)pp[want_row[l]] + poff;
+			ec_encode_data((int)size, (int)nc, nw, tbl.data(), in, out);
 			if (crcs)
 				for (int l = 0; l < nw; ++l)
 					crcs[w.block_count + (size_t)(b - r0) * rows + want_row[l]] =

@@ -192,6 +192,19 @@ def lib():
         [ctypes.c_void_p]
     L.lizec_chunk_write_host.restype = ctypes.c_int
     L.lizec_chunk_write_host.argtypes = write_args
+    L.lizec_degraded_write_table.restype = ctypes.c_int
+    L.lizec_degraded_write_table.argtypes = [
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32,
+        ctypes.c_uint32, ctypes.c_uint64, u8p, ctypes.c_int, u8p, u32p]
+    degraded_args = [
+        ctypes.c_int, u8p, ctypes.c_int, u32p, u32p, ctypes.c_void_p,
+        ctypes.c_int, u64p, u32p, ctypes.c_int, ctypes.c_int,
+        ctypes.c_uint32, u64p]
+    L.lizec_chunk_write_degraded_batch.restype = ctypes.c_int
+    L.lizec_chunk_write_degraded_batch.argtypes = [ctypes.c_void_p] + \
+        degraded_args + [ctypes.c_void_p]
+    L.lizec_chunk_write_degraded_host.restype = ctypes.c_int
+    L.lizec_chunk_write_degraded_host.argtypes = degraded_args
     _lib = L
     return _lib
 
