@@ -943,8 +943,8 @@ void lizec_host_free(void *p);
  *  sigs        : nchunks*oc signatures (sig_len bytes each), or NULL
  *  header_size : image header bytes; crc_off: CRC array offset within it
  *  host_dst    : nchunks*oc HOST addresses, header_size+part_len each
- *  sub_batch   : chunks per pipeline stage (0 = auto, ~1 GiB staging;
- *                clamped to nchunks)
+ *  sub_batch   : chunks per pipeline stage (0 = auto: 2 GiB of device
+ *                staging per slot, at most 64 chunks; clamped to nchunks)
  * Returns LIZEC_EINVAL from the host, with nothing allocated or enqueued
  * and no byte of the destinations written, for a NULL e, gftbls, host_src
  * or host_dst, nchunks < 1, ic or oc outside 1..32, part_len 0, not a
@@ -975,6 +975,111 @@ int lizec_replicate_run_interleaved(lizec_engine *e, uint64_t part_len, int ic,
                                     const uint64_t *host_src,
                                     const uint64_t *host_dst, int nchunks,
                                     int sub_batch);
+
+/* Streaming rebuild of chunks of ANY length and erasure pattern, sources
+ * verified: lizec_replicate_run with a block count per source and per
+ * destination of every chunk and a recover table per chunk — the job of
+ * ChunkReplicator::replicate as the reference does it, which asks each chunk
+ * for its own block count (chunk_replicator.cc:142-145), plans it from
+ * whatever parts are available (SliceRecoveryPlanner::prepare, :168) and
+ * checks every block it receives against the CRC that came with it
+ * (read_operation_executor.cc:261-263).
+ *  gftbls, ntables, tbl_index: as for lizec_ec_encode_batch_ragged;
+ *             tbl_index is a HOST array [nchunks] or NULL = table 0
+ *  host_src / src_nblocks: HOST arrays [nchunks][ic]: source j of chunk c is
+ *             src_nblocks[c][j] plain 64 KiB blocks, back to back at HOST
+ *             address host_src[c][j].  Blocks at or past a source's count are
+ *             the zeros past the chunk's end: not read, not copied, and they
+ *             need no buffer; an address whose count is 0 may be 0
+ *  host_src_crc: NULL, or a HOST array [nchunks][ic] of HOST addresses: the
+ *             source's CRC array, one big-endian CRC per block, 4 bytes
+ *             apart, at any alignment — what a MooseFS-format part file holds
+ *             at offset 1024 and what the replicator collects from its
+ *             READ_DATA packets.  0 = that slot is not verified.  Every block
+ *             below the source's count is hashed on the GPU after it lands
+ *             (csrc/replicate_stage.h) and compared; nothing past the count
+ *             is read, neither a data byte nor a CRC byte
+ *  bad_out  : HOST array [nchunks]; bit j of bad_out[c] is set iff a block
+ *             of source j of chunk c failed its check, 0 otherwise; complete
+ *             when the call returns.  The images are emitted either way (as
+ *             in lizec_chunk_read_verified_batch): a chunk whose mask is not
+ *             0 must be discarded.  Required with host_src_crc; without it
+ *             it may be NULL, and is zeroed if given
+ *  host_dst / dst_nblocks: HOST arrays [nchunks][oc]: destination l of chunk
+ *             c is an image of its own size at HOST address host_dst[c][l]:
+ *               MooseFS (flags 0): header_size + dst_nblocks*65536 bytes,
+ *                 signature at 0, the rest of the header zero, big-endian
+ *                 CRCs at crc_off, blocks at header_size — what
+ *                 lizec_replicate_run emits;
+ *               LIZEC_REPL_INTERLEAVED: dst_nblocks*65540 bytes, each block
+ *                 behind its CRC; sigs, sig_len, header_size and crc_off are
+ *                 unused.
+ *             A nonzero address with count 0 is a header-only MooseFS image,
+ *             or nothing at all in INTERLEAVED format.  Address 0 with count
+ *             0: the slot is not wanted.  Exactly the image's bytes are
+ *             written at each address.  A run in which no destination has a
+ *             block is legal and emits headers only
+ *  sigs     : nchunks*oc signatures (sig_len bytes each), or NULL = zeros
+ *  stage_bytes: device staging per pipeline slot; 0 = 2 GiB, what
+ *             lizec_replicate_run's auto sizing uses.  There are two slots.
+ *             The run is cut into stages by lizec_replicate_ragged_stages and
+ *             the slots are sized for the largest one
+ * Each stage runs in stream order on its slot's own stream: H2D of the
+ * sources into a packed arena, H2D of the stage's metadata (tables' index,
+ * block maps, counts, addresses, signatures and the sources' CRC bytes, one
+ * pinned block), one header kernel, the verify kernel if asked, the ragged
+ * EC kernel straight into the images, the CRC fill with per-image counts,
+ * D2H of each image and of the stage's masks.  Zero-length copies are
+ * skipped.  All scratch lives in the slots and is freed before the call
+ * returns; the engine's per-stream scratch is not used.
+ * Returns LIZEC_EINVAL from the host, with nothing allocated or enqueued and
+ * no byte of the destinations or of bad_out written, for a NULL e, gftbls,
+ * host_src, src_nblocks, host_dst or dst_nblocks, nchunks < 1, ic or oc
+ * outside 1..32, a tbl_index entry >= ntables, ntables outside the limits of
+ * the multi call, a count above 1024, a nonzero count with address 0,
+ * bad_out == NULL with host_src_crc != NULL, an unknown flag bit,
+ * stage_bytes above 2^31, more block rows in the run than
+ * lizec_ragged_block_map accepts, and for MooseFS images a header_size that
+ * is not a multiple of 16, sig_len > header_size or a CRC array that does
+ * not fit (crc_off + 4*max(dst_nblocks) > header_size).  Use
+ * lizec_host_alloc'd buffers for real overlap; pageable ones stay correct. */
+#define LIZEC_REPL_INTERLEAVED 1u   /* images in INTERLEAVED format; else MooseFS */
+int lizec_replicate_run_ragged(
+    lizec_engine *e, int ic, int oc, const uint8_t *gftbls, int ntables,
+    const uint32_t *tbl_index, const uint64_t *host_src,
+    const uint32_t *src_nblocks, const uint64_t *host_src_crc,
+    const uint8_t *sigs, uint32_t sig_len, uint32_t header_size,
+    uint32_t crc_off, const uint64_t *host_dst, const uint32_t *dst_nblocks,
+    int nchunks, uint64_t stage_bytes, uint32_t flags, uint32_t *bad_out);
+
+/* The stage cut of lizec_replicate_run_ragged (pure host, no GPU; the GPU
+ * call uses exactly this function).  A chunk's footprint is its source bytes
+ * (counts * 65536) plus the bytes of its wanted images (host_dst != 0), each
+ * image rounded up to 16.  A stage takes chunks in order while the sum of
+ * their footprints stays within stage_bytes (0 = 2 GiB); a chunk that alone
+ * exceeds stage_bytes is a stage of its own.
+ *  stage_first: receives stages + 1 entries — stage i is chunks
+ *             [stage_first[i], stage_first[i + 1]) — or NULL to count only
+ *  cap      : room in stage_first, in entries
+ * Returns the number of stages, or LIZEC_EINVAL for a NULL array, nchunks
+ * < 1, ic or oc outside 1..32, a count above 1024, an unknown flag bit,
+ * stage_bytes above 2^31, or stages + 1 > cap. */
+int64_t lizec_replicate_ragged_stages(
+    int ic, int oc, const uint32_t *src_nblocks, const uint64_t *host_dst,
+    const uint32_t *dst_nblocks, int nchunks, uint32_t header_size,
+    uint32_t flags, uint64_t stage_bytes, uint32_t *stage_first,
+    uint64_t cap);
+
+/* The same rebuild on the host, byte for byte, images and bad_out: the
+ * no-GPU floor of the path.  Same arguments without e and stage_bytes, same
+ * refusals (nothing written). */
+int lizec_replicate_ragged_host(
+    int ic, int oc, const uint8_t *gftbls, int ntables,
+    const uint32_t *tbl_index, const uint64_t *host_src,
+    const uint32_t *src_nblocks, const uint64_t *host_src_crc,
+    const uint8_t *sigs, uint32_t sig_len, uint32_t header_size,
+    uint32_t crc_off, const uint64_t *host_dst, const uint32_t *dst_nblocks,
+    int nchunks, uint32_t flags, uint32_t *bad_out);
 
 #ifdef __cplusplus
 }

@@ -48,6 +48,7 @@
 #include "crc_ranges.h"
 #include "read_gate.h"
 #include "read_verify.h"
+#include "replicate_stage.h"
 #include "ec_kernel_write.h"
 #include "ec_kernel_write_degraded.h"
 
@@ -923,6 +924,35 @@ static void launch_ec_ragged(uint32_t entries, int srcs, int dest_base,
 #undef LIZEC_LAUNCH_RAGGED
 }
 
+/* Every pass of a ragged batch: at most 8 destinations each, as
+ * run_batch_strided.  Shared by lizec_ec_encode_batch_ragged and the ragged
+ * streaming rebuild, which keeps the device arrays in its own slots. */
+static void launch_ec_ragged_passes(uint32_t entries, int srcs, int dests,
+                                    const ragged_dev &rd,
+                                    uint32_t src_block_stride,
+                                    uint32_t dst_block_stride, bool sal,
+                                    bool dal, hipStream_t s) {
+	for (int base = 0; base < dests;) {
+		int d = dests - base;
+		if (d > 8) d = 8;
+#define LIZEC_LAUNCH_RAGGED_D(D)                                           \
+	launch_ec_ragged<D>(entries, srcs, base, rd, dests, src_block_stride,  \
+	                    dst_block_stride, sal, dal, s)
+		switch (d) {
+		case 1: LIZEC_LAUNCH_RAGGED_D(1); break;
+		case 2: LIZEC_LAUNCH_RAGGED_D(2); break;
+		case 3: LIZEC_LAUNCH_RAGGED_D(3); break;
+		case 4: LIZEC_LAUNCH_RAGGED_D(4); break;
+		case 5: LIZEC_LAUNCH_RAGGED_D(5); break;
+		case 6: LIZEC_LAUNCH_RAGGED_D(6); break;
+		case 7: LIZEC_LAUNCH_RAGGED_D(7); break;
+		default: LIZEC_LAUNCH_RAGGED_D(8); break;
+		}
+#undef LIZEC_LAUNCH_RAGGED_D
+		base += d;
+	}
+}
+
 extern "C" int lizec_ec_encode_batch_ragged(
     lizec_engine *e, int srcs, int dests, const uint8_t *gftbls, int ntables,
     const uint32_t *tbl_index, const uint64_t *src_dptrs,
@@ -1010,26 +1040,8 @@ extern "C" int lizec_ec_encode_batch_ragged(
 	rd.dst_nb = (const uint32_t *)(c->d_ragged + o_dnb);
 	rd.src = c->d_ptrs;
 	rd.dst = c->d_ptrs + nsrc;
-	/* passes of at most 8 destinations, as run_batch_strided */
-	for (int base = 0; base < dests;) {
-		int d = dests - base;
-		if (d > 8) d = 8;
-#define LIZEC_LAUNCH_RAGGED_D(D)                                           \
-	launch_ec_ragged<D>((uint32_t)entries, srcs, base, rd, dests,          \
-	                    src_block_stride, dst_block_stride, sal, dal, s)
-		switch (d) {
-		case 1: LIZEC_LAUNCH_RAGGED_D(1); break;
-		case 2: LIZEC_LAUNCH_RAGGED_D(2); break;
-		case 3: LIZEC_LAUNCH_RAGGED_D(3); break;
-		case 4: LIZEC_LAUNCH_RAGGED_D(4); break;
-		case 5: LIZEC_LAUNCH_RAGGED_D(5); break;
-		case 6: LIZEC_LAUNCH_RAGGED_D(6); break;
-		case 7: LIZEC_LAUNCH_RAGGED_D(7); break;
-		default: LIZEC_LAUNCH_RAGGED_D(8); break;
-		}
-#undef LIZEC_LAUNCH_RAGGED_D
-		base += d;
-	}
+	launch_ec_ragged_passes((uint32_t)entries, srcs, dests, rd,
+	                        src_block_stride, dst_block_stride, sal, dal, s);
 	LIZEC_CHECK(hipGetLastError());
 	return LIZEC_OK;
 }
@@ -2779,4 +2791,358 @@ extern "C" int lizec_replicate_run_interleaved(
 	                         kHddBlock, kHddBlock};
 	return replicate_run_impl(e, part_len, ic, oc, gftbls, host_src, nullptr,
 	                          0u, lay, host_dst, nchunks, sub_batch);
+}
+
+/* ------------------------------------------------------------------ */
+/* Ragged streaming rebuild (replicate_stage.h)                       */
+/* ------------------------------------------------------------------ */
+
+extern "C" int lizec_impl_replicate_ragged_check(
+    int ic, int oc, const uint8_t *gftbls, int ntables,
+    const uint32_t *tbl_index, const uint64_t *host_src,
+    const uint32_t *src_nblocks, const uint64_t *host_src_crc,
+    const uint8_t *sigs, uint32_t sig_len, uint32_t header_size,
+    uint32_t crc_off, const uint64_t *host_dst, const uint32_t *dst_nblocks,
+    int nchunks, uint64_t stage_bytes, uint32_t flags,
+    const uint32_t *bad_out);
+
+/* One double-buffer slot of the ragged pipeline.  Everything a stage's
+ * kernels read besides the tables lives here — nothing goes through the
+ * engine's per-stream scratch, so nothing is left behind under the handle
+ * of a stream that dies with the call. */
+struct repl_ragged_slot {
+	hipStream_t stream = nullptr;
+	hipEvent_t done = nullptr;
+	uint8_t *d_arena = nullptr;   /* sources, then images, 16-aligned each */
+	uint8_t *d_meta = nullptr;    /* repl_stage_meta */
+	uint8_t *h_meta = nullptr;    /* pinned mirror */
+	bool used = false;
+};
+
+static void repl_ragged_slot_free(repl_ragged_slot &sl) {
+	(void)hipFree(sl.d_arena);
+	(void)hipFree(sl.d_meta);
+	(void)hipHostFree(sl.h_meta);
+	if (sl.done) (void)hipEventDestroy(sl.done);
+	if (sl.stream) (void)hipStreamDestroy(sl.stream);
+	sl = repl_ragged_slot();
+}
+
+/* A stage's metadata block: byte offsets of its sections, each 16-aligned.
+ * One pinned block, one H2D per stage. */
+struct repl_stage_meta {
+	size_t index;   /* u32 [n]: table of every chunk */
+	size_t dmap;    /* uint2 [rows]: block rows of the destinations */
+	size_t smap;    /* uint2 [srows]: block rows of the sources (verify) */
+	size_t snb;     /* u32 [n][ic] */
+	size_t dnb;     /* u32 [n][oc] */
+	size_t src;     /* u64 [n][ic]: staged sources */
+	size_t dst;     /* u64 [n][oc]: block 0 of every image */
+	size_t img;     /* u64 [n][oc]: images, 0 = not wanted */
+	size_t doff;    /* u32 [n][oc] x 3: data offset, CRC offset, count */
+	size_t crcp;    /* u64 [n][ic]: staged CRC bytes, 0 = not verified */
+	size_t bad;     /* u32 [n]: the masks, uploaded as zeros */
+	size_t sig;     /* u8 [n][oc][sig_len] */
+	size_t crc;     /* u8: the sources' CRC bytes, back to back */
+	size_t bytes;
+};
+
+static repl_stage_meta repl_stage_layout(size_t n, int ic, int oc,
+                                         size_t rows, size_t srows,
+                                         size_t sig_bytes, size_t crc_bytes) {
+	auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+	repl_stage_meta m;
+	m.index = 0;
+	m.dmap = m.index + up16(n * 4);
+	m.smap = m.dmap + up16(rows * 8);
+	m.snb = m.smap + up16(srows * 8);
+	m.dnb = m.snb + up16(n * ic * 4);
+	m.src = m.dnb + up16(n * oc * 4);
+	m.dst = m.src + up16(n * ic * 8);
+	m.img = m.dst + up16(n * oc * 8);
+	m.doff = m.img + up16(n * oc * 8);
+	m.crcp = m.doff + up16(n * oc * 12);
+	m.bad = m.crcp + up16(n * ic * 8);
+	m.sig = m.bad + up16(n * 4);
+	m.crc = m.sig + up16(sig_bytes);
+	m.bytes = m.crc + up16(crc_bytes);
+	return m;
+}
+
+/* What one stage needs: counted once to size the slots, and again when the
+ * stage is laid out. */
+struct repl_stage_need {
+	uint64_t arena;        /* sources + wanted images, 16-rounded each */
+	int64_t rows, srows;   /* block rows of destinations / of sources */
+	size_t crc_bytes;
+	uint32_t max_dst;
+};
+
+extern "C" int lizec_replicate_run_ragged(
+    lizec_engine *e, int ic, int oc, const uint8_t *gftbls, int ntables,
+    const uint32_t *tbl_index, const uint64_t *host_src,
+    const uint32_t *src_nblocks, const uint64_t *host_src_crc,
+    const uint8_t *sigs, uint32_t sig_len, uint32_t header_size,
+    uint32_t crc_off, const uint64_t *host_dst, const uint32_t *dst_nblocks,
+    int nchunks, uint64_t stage_bytes, uint32_t flags, uint32_t *bad_out) {
+	if (!e) return LIZEC_EINVAL;
+	int rc = lizec_impl_replicate_ragged_check(
+	    ic, oc, gftbls, ntables, tbl_index, host_src, src_nblocks,
+	    host_src_crc, sigs, sig_len, header_size, crc_off, host_dst,
+	    dst_nblocks, nchunks, stage_bytes, flags, bad_out);
+	if (rc != LIZEC_OK) return rc;
+	const bool il = (flags & LIZEC_REPL_INTERLEAVED) != 0;
+	constexpr uint32_t kHddBlock = kECBlockBytes + 4;   /* chunk.h:40 */
+	const uint32_t hdr = il ? 0u : header_size;
+	const uint32_t data_off = il ? 4u : header_size;
+	const uint32_t coff = il ? 0u : crc_off;
+	const uint32_t bstride = il ? kHddBlock : kECBlockBytes;
+	const uint32_t cstride = il ? kHddBlock : 4u;
+	const size_t sigl = il || !sigs ? 0 : sig_len;
+	auto image_bytes = [&](size_t slot) -> uint64_t {
+		if (!host_dst[slot]) return 0;
+		return hdr + (uint64_t)dst_nblocks[slot] * bstride;
+	};
+
+	int64_t nst = lizec_replicate_ragged_stages(
+	    ic, oc, src_nblocks, host_dst, dst_nblocks, nchunks, header_size,
+	    flags, stage_bytes, nullptr, 0);
+	if (nst < 1) return LIZEC_EINVAL;
+	uint32_t *first = (uint32_t *)malloc(((size_t)nst + 1) * 4);
+	if (!first) return LIZEC_ENOMEM;
+	if (lizec_replicate_ragged_stages(ic, oc, src_nblocks, host_dst,
+	                                  dst_nblocks, nchunks, header_size, flags,
+	                                  stage_bytes, first,
+	                                  (uint64_t)nst + 1) != nst) {
+		free(first);
+		return LIZEC_EINVAL;
+	}
+	auto need_of = [&](int64_t i) {
+		const uint32_t c0 = first[i], n = first[i + 1] - c0;
+		repl_stage_need nd = {0, 0, 0, 0, 0};
+		for (size_t s = (size_t)c0 * ic; s < (size_t)(c0 + n) * ic; ++s) {
+			nd.arena += (uint64_t)src_nblocks[s] * kECBlockBytes;
+			if (host_src_crc && host_src_crc[s])
+				nd.crc_bytes += (size_t)src_nblocks[s] * 4;
+		}
+		for (size_t s = (size_t)c0 * oc; s < (size_t)(c0 + n) * oc; ++s) {
+			nd.arena += (image_bytes(s) + 15) & ~(uint64_t)15;
+			if (dst_nblocks[s] > nd.max_dst) nd.max_dst = dst_nblocks[s];
+		}
+		nd.rows = lizec_ragged_block_map(dst_nblocks + (size_t)c0 * oc, oc,
+		                                 (int)n, nullptr, 0);
+		if (host_src_crc)
+			nd.srows = lizec_ragged_block_map(src_nblocks + (size_t)c0 * ic,
+			                                  ic, (int)n, nullptr, 0);
+		return nd;
+	};
+	/* the slots are sized for the largest stage */
+	uint64_t arena_max = 16;
+	size_t meta_max = 0;
+	for (int64_t i = 0; i < nst; ++i) {
+		const repl_stage_need nd = need_of(i);
+		if (nd.rows < 0 || nd.srows < 0) {
+			free(first);
+			return LIZEC_EINVAL;
+		}
+		const size_t n = first[i + 1] - first[i];
+		const size_t mb = repl_stage_layout(n, ic, oc, (size_t)nd.rows,
+		                                    (size_t)nd.srows, n * oc * sigl,
+		                                    nd.crc_bytes).bytes;
+		if (nd.arena > arena_max) arena_max = nd.arena;
+		if (mb > meta_max) meta_max = mb;
+	}
+	if (bad_out && !host_src_crc) memset(bad_out, 0, (size_t)nchunks * 4);
+
+	if (hipSetDevice(e->device) != hipSuccess) {
+		free(first);
+		return LIZEC_EHIP;
+	}
+	const size_t tbl_bytes = (size_t)kECTblBytes * ntables * ic * oc;
+	uint8_t *d_tbl = nullptr, *h_tbl = (uint8_t *)malloc(tbl_bytes);
+	repl_ragged_slot sl[2];
+	if (!h_tbl) rc = LIZEC_ENOMEM;
+	if (rc == LIZEC_OK) {
+		for (size_t i = 0; i < (size_t)ntables * ic * oc; ++i)
+			pack_mixed_radix(gftbls + i * 32, h_tbl + i * kECTblBytes);
+		if (hipMalloc(&d_tbl, tbl_bytes) != hipSuccess)
+			rc = LIZEC_ENOMEM;
+		else if (hipMemcpy(d_tbl, h_tbl, tbl_bytes, hipMemcpyHostToDevice) !=
+		         hipSuccess)
+			rc = LIZEC_EHIP;
+	}
+	for (int i = 0; i < 2 && i < nst && rc == LIZEC_OK; ++i) {
+		if (hipStreamCreate(&sl[i].stream) != hipSuccess ||
+		    hipEventCreateWithFlags(&sl[i].done, hipEventDisableTiming) !=
+		        hipSuccess ||
+		    hipMalloc(&sl[i].d_arena, arena_max) != hipSuccess ||
+		    hipMalloc(&sl[i].d_meta, meta_max) != hipSuccess ||
+		    hipHostMalloc(&sl[i].h_meta, meta_max) != hipSuccess)
+			rc = LIZEC_ENOMEM;
+	}
+
+	for (int64_t i = 0; i < nst && rc == LIZEC_OK; ++i) {
+		const uint32_t c0 = first[i], n = first[i + 1] - c0;
+		const repl_stage_need nd = need_of(i);
+		const repl_stage_meta m =
+		    repl_stage_layout(n, ic, oc, (size_t)nd.rows, (size_t)nd.srows,
+		                      (size_t)n * oc * sigl, nd.crc_bytes);
+		repl_ragged_slot &s = sl[i & 1];
+		hipStream_t st = s.stream;
+		if (s.used && hipEventSynchronize(s.done) != hipSuccess) {
+			rc = LIZEC_EHIP;
+			break;
+		}
+		s.used = true;
+		/* lay the stage out (host side; the slot is idle now) */
+		uint8_t *h = s.h_meta;
+		const size_t nsrc = (size_t)n * ic, ndst = (size_t)n * oc;
+		const uint64_t *hs = host_src + (size_t)c0 * ic;
+		const uint64_t *hd = host_dst + (size_t)c0 * oc;
+		const uint32_t *sn = src_nblocks + (size_t)c0 * ic;
+		const uint32_t *dn = dst_nblocks + (size_t)c0 * oc;
+		if (tbl_index)
+			memcpy(h + m.index, tbl_index + c0, (size_t)n * 4);
+		else
+			memset(h + m.index, 0, (size_t)n * 4);
+		if ((nd.rows &&
+		     lizec_ragged_block_map(dn, oc, (int)n, (uint32_t *)(h + m.dmap),
+		                            (uint64_t)nd.rows) != nd.rows) ||
+		    (nd.srows &&
+		     lizec_ragged_block_map(sn, ic, (int)n, (uint32_t *)(h + m.smap),
+		                            (uint64_t)nd.srows) != nd.srows)) {
+			rc = LIZEC_EINVAL;
+			break;
+		}
+		memcpy(h + m.snb, sn, nsrc * 4);
+		memcpy(h + m.dnb, dn, ndst * 4);
+		uint64_t *h_src = (uint64_t *)(h + m.src);
+		uint64_t *h_dst = (uint64_t *)(h + m.dst);
+		uint64_t *h_img = (uint64_t *)(h + m.img);
+		uint32_t *h_doff = (uint32_t *)(h + m.doff);
+		uint32_t *h_coff = h_doff + ndst, *h_cnt = h_coff + ndst;
+		uint64_t *h_crcp = (uint64_t *)(h + m.crcp);
+		uint64_t off = 0;
+		size_t crc_at = m.crc;
+		for (size_t k = 0; k < nsrc; ++k) {
+			h_src[k] = sn[k] ? (uint64_t)(s.d_arena + off) : 0;
+			off += (uint64_t)sn[k] * kECBlockBytes;
+			h_crcp[k] = 0;
+			const uint64_t crcs = host_src_crc ? host_src_crc[(size_t)c0 * ic + k] : 0;
+			if (crcs) {
+				/* the CRC bytes travel with the metadata; a slot of no
+				 * blocks keeps an address, which is never read */
+				h_crcp[k] = (uint64_t)(s.d_meta + crc_at);
+				memcpy(h + crc_at, (const void *)crcs, (size_t)sn[k] * 4);
+				crc_at += (size_t)sn[k] * 4;
+			}
+		}
+		const uint64_t img0 = off;
+		for (size_t k = 0; k < ndst; ++k) {
+			const uint64_t bytes = image_bytes((size_t)c0 * oc + k);
+			h_img[k] = hd[k] ? (uint64_t)(s.d_arena + off) : 0;
+			h_dst[k] = dn[k] ? h_img[k] + data_off : 0;
+			h_doff[k] = data_off;
+			h_coff[k] = coff;
+			h_cnt[k] = dn[k];
+			off += (bytes + 15) & ~(uint64_t)15;
+		}
+		memset(h + m.bad, 0, (size_t)n * 4);
+		if (sigl)
+			memcpy(h + m.sig, sigs + (size_t)c0 * oc * sigl, ndst * sigl);
+		/* enqueue the stage: H2D parts and metadata, headers, verify,
+		 * recover, CRC, D2H */
+		off = 0;
+		for (size_t k = 0; k < nsrc && rc == LIZEC_OK; ++k) {
+			const uint64_t bytes = (uint64_t)sn[k] * kECBlockBytes;
+			if (bytes &&
+			    hipMemcpyAsync(s.d_arena + off, (const void *)hs[k], bytes,
+			                   hipMemcpyHostToDevice, st) != hipSuccess)
+				rc = LIZEC_EHIP;
+			off += bytes;
+		}
+		if (rc != LIZEC_OK) break;
+		if (hipMemcpyAsync(s.d_meta, h, m.bytes, hipMemcpyHostToDevice, st) !=
+		    hipSuccess) {
+			rc = LIZEC_EHIP;
+			break;
+		}
+		uint8_t *d = s.d_meta;
+		if (hdr)
+			hipLaunchKernelGGL(replicate_header_kernel, dim3((uint32_t)ndst),
+			                   dim3(kReplHeaderThreads), 0, st,
+			                   (const uint64_t *)(d + m.img), d + m.sig,
+			                   (uint32_t)sigl, hdr);
+		if (nd.srows) {
+			/* one wave per (source block row, slot), four per workgroup */
+			const uint64_t items = (uint64_t)nd.srows * ic;
+			hipLaunchKernelGGL(replicate_verify_kernel,
+			                   dim3((uint32_t)((items + 3) / 4)),
+			                   dim3(kCrcRangesThreads), 0, st, ic, items,
+			                   (const uint2 *)(d + m.smap),
+			                   (const uint64_t *)(d + m.src),
+			                   (const uint64_t *)(d + m.crcp),
+			                   (const uint32_t *)(d + m.snb), e->d_crc_const,
+			                   e->d_crc_const + kCrcTabWords,
+			                   (uint32_t *)(d + m.bad));
+		}
+		if (nd.rows) {
+			/* a stage without a block reaches neither launch: both refuse
+			 * an empty batch */
+			ragged_dev rd;
+			rd.tbls = d_tbl;
+			rd.index = (const uint32_t *)(d + m.index);
+			rd.map = (const uint2 *)(d + m.dmap);
+			rd.src = (const uint64_t *)(d + m.src);
+			rd.dst = (const uint64_t *)(d + m.dst);
+			rd.src_nb = (const uint32_t *)(d + m.snb);
+			rd.dst_nb = (const uint32_t *)(d + m.dnb);
+			/* staged sources are 16-aligned; MooseFS blocks too, INTERLEAVED
+			 * ones sit at 4 + 65540*b and take the 4-byte path */
+			launch_ec_ragged_passes((uint32_t)nd.rows, ic, oc, rd,
+			                        kECBlockBytes, bstride, true, !il, st);
+			if (hipGetLastError() != hipSuccess) {
+				rc = LIZEC_EHIP;
+				break;
+			}
+			rc = image_crc_launch(e, (const uint64_t *)(d + m.img),
+			                      (const uint32_t *)(d + m.doff),
+			                      (const uint32_t *)(d + m.doff) + ndst,
+			                      (const uint32_t *)(d + m.doff) + 2 * ndst,
+			                      (int)ndst, nd.max_dst, bstride, cstride, st);
+			if (rc != LIZEC_OK) break;
+		}
+		if (hipGetLastError() != hipSuccess) {
+			rc = LIZEC_EHIP;
+			break;
+		}
+		off = img0;
+		for (size_t k = 0; k < ndst && rc == LIZEC_OK; ++k) {
+			const uint64_t bytes = image_bytes((size_t)c0 * oc + k);
+			if (bytes &&
+			    hipMemcpyAsync((void *)hd[k], s.d_arena + off, bytes,
+			                   hipMemcpyDeviceToHost, st) != hipSuccess)
+				rc = LIZEC_EHIP;
+			off += (bytes + 15) & ~(uint64_t)15;
+		}
+		if (rc != LIZEC_OK) break;
+		if (host_src_crc &&
+		    hipMemcpyAsync(bad_out + c0, d + m.bad, (size_t)n * 4,
+		                   hipMemcpyDeviceToHost, st) != hipSuccess) {
+			rc = LIZEC_EHIP;
+			break;
+		}
+		if (hipEventRecord(s.done, st) != hipSuccess) rc = LIZEC_EHIP;
+	}
+	for (int i = 0; i < 2; ++i) {
+		if (sl[i].used && sl[i].stream &&
+		    hipStreamSynchronize(sl[i].stream) != hipSuccess &&
+		    rc == LIZEC_OK)
+			rc = LIZEC_EHIP;
+		repl_ragged_slot_free(sl[i]);
+	}
+	(void)hipFree(d_tbl);
+	free(h_tbl);
+	free(first);
+	return rc;
 }

@@ -1273,3 +1273,209 @@ extern "C" int lizec_chunk_write_degraded_host(
 	}
 	return LIZEC_OK;
 }
+
+/* ------------------------------------------------------------------ */
+/* Ragged streaming rebuild: checks, stage cut and host twin          */
+/* (pure host)                                                        */
+/* ------------------------------------------------------------------ */
+
+namespace {
+
+constexpr uint64_t kReplBlock = 65536;          /* MFSBLOCKSIZE */
+constexpr uint64_t kReplHddBlock = 65536 + 4;   /* chunk.h:40 kHddBlockSize */
+constexpr uint64_t kReplStageDefault = (uint64_t)1 << 31;
+
+/* Bytes of the image of `nb` blocks; 0 = nothing to emit. */
+inline uint64_t repl_image_bytes(uint32_t nb, uint32_t header_size,
+                                 uint32_t flags) {
+	return (flags & LIZEC_REPL_INTERLEAVED) ? nb * kReplHddBlock
+	                                        : header_size + nb * kReplBlock;
+}
+
+}  // namespace
+
+/* Every argument check of lizec_replicate_run_ragged, shared with
+ * lizec_replicate_ragged_host; see lizec.h. */
+extern "C" int lizec_impl_replicate_ragged_check(
+    int ic, int oc, const uint8_t *gftbls, int ntables,
+    const uint32_t *tbl_index, const uint64_t *host_src,
+    const uint32_t *src_nblocks, const uint64_t *host_src_crc,
+    const uint8_t *sigs, uint32_t sig_len, uint32_t header_size,
+    uint32_t crc_off, const uint64_t *host_dst, const uint32_t *dst_nblocks,
+    int nchunks, uint64_t stage_bytes, uint32_t flags,
+    const uint32_t *bad_out) {
+	(void)sigs;   /* NULL leaves the signature block zero */
+	if (!gftbls || !host_src || !src_nblocks || !host_dst || !dst_nblocks ||
+	    nchunks < 1)
+		return LIZEC_EINVAL;
+	if (ic < 1 || ic > 32 || oc < 1 || oc > 32) return LIZEC_EINVAL;
+	if (flags & ~LIZEC_REPL_INTERLEAVED) return LIZEC_EINVAL;
+	if (stage_bytes > kReplStageDefault) return LIZEC_EINVAL;
+	if (host_src_crc && !bad_out) return LIZEC_EINVAL;
+	if (ntables < 1 || (uint64_t)ntables * 32 * ic * oc > (uint64_t)1 << 30)
+		return LIZEC_EINVAL;
+	if (tbl_index)
+		for (int c = 0; c < nchunks; ++c)
+			if (tbl_index[c] >= (uint32_t)ntables) return LIZEC_EINVAL;
+	const size_t nsrc = (size_t)nchunks * ic, ndst = (size_t)nchunks * oc;
+	for (size_t i = 0; i < nsrc; ++i) {
+		if (src_nblocks[i] > 1024u) return LIZEC_EINVAL;
+		if (src_nblocks[i] && !host_src[i]) return LIZEC_EINVAL;
+	}
+	uint32_t max_dst = 0;
+	for (size_t i = 0; i < ndst; ++i) {
+		if (dst_nblocks[i] > 1024u) return LIZEC_EINVAL;
+		if (dst_nblocks[i] && !host_dst[i]) return LIZEC_EINVAL;
+		if (dst_nblocks[i] > max_dst) max_dst = dst_nblocks[i];
+	}
+	/* a stage's block rows are one ragged EC batch (8 KiB tiles in a 31-bit
+	 * grid); bounding the whole run bounds every stage */
+	if ((uint64_t)nchunks * max_dst * 8 > 0x7FFFFFFFull &&
+	    lizec_ragged_block_map(dst_nblocks, oc, nchunks, nullptr, 0) < 0)
+		return LIZEC_EINVAL;
+	if (!(flags & LIZEC_REPL_INTERLEAVED)) {
+		/* the staged images start 16-aligned and their blocks, header_size
+		 * in, are written with 16-byte vector accesses */
+		if (header_size % 16 || sig_len > header_size ||
+		    (uint64_t)crc_off + 4 * (uint64_t)max_dst > header_size)
+			return LIZEC_EINVAL;
+	}
+	return LIZEC_OK;
+}
+
+extern "C" int64_t lizec_replicate_ragged_stages(
+    int ic, int oc, const uint32_t *src_nblocks, const uint64_t *host_dst,
+    const uint32_t *dst_nblocks, int nchunks, uint32_t header_size,
+    uint32_t flags, uint64_t stage_bytes, uint32_t *stage_first,
+    uint64_t cap) {
+	if (!src_nblocks || !host_dst || !dst_nblocks || nchunks < 1 || ic < 1 ||
+	    ic > 32 || oc < 1 || oc > 32 || (flags & ~LIZEC_REPL_INTERLEAVED) ||
+	    stage_bytes > kReplStageDefault)
+		return LIZEC_EINVAL;
+	if (!stage_bytes) stage_bytes = kReplStageDefault;
+	uint64_t stages = 0, sum = 0;
+	for (int c = 0; c < nchunks; ++c) {
+		uint64_t foot = 0;
+		for (int j = 0; j < ic; ++j) {
+			if (src_nblocks[(size_t)c * ic + j] > 1024u) return LIZEC_EINVAL;
+			foot += src_nblocks[(size_t)c * ic + j] * kReplBlock;
+		}
+		for (int l = 0; l < oc; ++l) {
+			const size_t n = (size_t)c * oc + l;
+			if (dst_nblocks[n] > 1024u) return LIZEC_EINVAL;
+			if (!host_dst[n]) continue;   /* not wanted: no image staged */
+			foot += (repl_image_bytes(dst_nblocks[n], header_size, flags) +
+			         15) & ~(uint64_t)15;
+		}
+		/* a chunk opens a stage if it is the first, or does not fit behind
+		 * the ones the open stage holds */
+		if (c == 0 || sum + foot > stage_bytes) {
+			if (stage_first) {
+				if (stages + 1 >= cap) return LIZEC_EINVAL;
+				stage_first[stages] = (uint32_t)c;
+			}
+			++stages;
+			sum = 0;
+		}
+		sum += foot;
+	}
+	if (stage_first) stage_first[stages] = (uint32_t)nchunks;
+	return (int64_t)stages;
+}
+
+/* lizec_replicate_run_ragged on the host, chunk by chunk: lizec_crc32 over
+ * every counted source block that has a CRC, ec_encode_data per block row
+ * over the sources that have the row, lizec_crc32 over what it wrote. */
+extern "C" int lizec_replicate_ragged_host(
+    int ic, int oc, const uint8_t *gftbls, int ntables,
+    const uint32_t *tbl_index, const uint64_t *host_src,
+    const uint32_t *src_nblocks, const uint64_t *host_src_crc,
+    const uint8_t *sigs, uint32_t sig_len, uint32_t header_size,
+    uint32_t crc_off, const uint64_t *host_dst, const uint32_t *dst_nblocks,
+    int nchunks, uint32_t flags, uint32_t *bad_out) {
+	int r = lizec_impl_replicate_ragged_check(
+	    ic, oc, gftbls, ntables, tbl_index, host_src, src_nblocks,
+	    host_src_crc, sigs, sig_len, header_size, crc_off, host_dst,
+	    dst_nblocks, nchunks, 0, flags, bad_out);
+	if (r != LIZEC_OK) return r;
+	lizec_crc32_init();
+	const bool il = (flags & LIZEC_REPL_INTERLEAVED) != 0;
+	const uint64_t data_off = il ? 4 : header_size;
+	const uint64_t coff = il ? 0 : crc_off;
+	const uint64_t bstride = il ? kReplHddBlock : kReplBlock;
+	const uint64_t cstride = il ? kReplHddBlock : 4;
+	std::vector<uint8_t> tbl((size_t)32 * 32 * 32);   /* wanted rows, closed up */
+	for (int c = 0; c < nchunks; ++c) {
+		const uint64_t *sp = host_src + (size_t)c * ic;
+		const uint32_t *sn = src_nblocks + (size_t)c * ic;
+		const uint64_t *dp = host_dst + (size_t)c * oc;
+		const uint32_t *dn = dst_nblocks + (size_t)c * oc;
+		if (bad_out) {
+			uint32_t bad = 0;
+			for (int j = 0; host_src_crc && j < ic; ++j) {
+				const uint8_t *q =
+				    (const uint8_t *)(uintptr_t)host_src_crc[(size_t)c * ic + j];
+				if (!q) continue;
+				for (uint32_t b = 0; b < sn[j]; ++b, q += 4) {
+					const uint32_t want = ((uint32_t)q[0] << 24) |
+					                      ((uint32_t)q[1] << 16) |
+					                      ((uint32_t)q[2] << 8) | q[3];
+					if (lizec_crc32(0, (const uint8_t *)(uintptr_t)sp[j] +
+					                       b * kReplBlock, 65536) != want)
+						bad |= 1u << j;
+				}
+			}
+			bad_out[c] = bad;
+		}
+		const uint8_t *t =
+		    gftbls + (size_t)(tbl_index ? tbl_index[c] : 0) * 32 * ic * oc;
+		uint32_t rows = 0;
+		for (int l = 0; l < oc; ++l) {
+			if (!dp[l]) continue;
+			if (dn[l] > rows) rows = dn[l];
+			if (il) continue;
+			uint8_t *img = (uint8_t *)(uintptr_t)dp[l];
+			memset(img, 0, header_size);
+			if (sigs && sig_len)
+				memcpy(img, sigs + ((size_t)c * oc + l) * sig_len, sig_len);
+		}
+		for (uint32_t b = 0; b < rows; ++b) {
+			uint8_t *in[32], *out[32];
+			int row[32], np = 0, nw = 0;
+			for (int l = 0; l < oc; ++l)
+				if (b < dn[l]) {
+					row[nw] = l;
+					out[nw++] = (uint8_t *)(uintptr_t)dp[l] + data_off +
+					            b * bstride;
+				}
+			for (int j = 0; j < ic; ++j) {
+				if (b >= sn[j]) continue;
+				for (int l = 0; l < nw; ++l)
+					memcpy(tbl.data() + ((size_t)l * ic + np) * 32,
+					       t + ((size_t)row[l] * ic + j) * 32, 32);
+				in[np++] = (uint8_t *)(uintptr_t)sp[j] + b * kReplBlock;
+			}
+			if (!np) {
+				for (int l = 0; l < nw; ++l) memset(out[l], 0, 65536);
+			} else {
+				/* the table was filled at row pitch ic; close it up to np */
+				if (np < ic)
+					for (int l = 1; l < nw; ++l)
+						memmove(tbl.data() + (size_t)l * np * 32,
+						        tbl.data() + (size_t)l * ic * 32,
+						        (size_t)np * 32);
+				ec_encode_data(65536, np, nw, tbl.data(), in, out);
+			}
+			for (int l = 0; l < nw; ++l) {
+				const uint32_t crc = lizec_crc32(0, out[l], 65536);
+				uint8_t *q = (uint8_t *)(uintptr_t)dp[row[l]] + coff +
+				             b * cstride;
+				q[0] = (uint8_t)(crc >> 24);
+				q[1] = (uint8_t)(crc >> 16);
+				q[2] = (uint8_t)(crc >> 8);
+				q[3] = (uint8_t)crc;
+			}
+		}
+	}
+	return LIZEC_OK;
+}

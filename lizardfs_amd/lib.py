@@ -205,6 +205,24 @@ def lib():
         degraded_args + [ctypes.c_void_p]
     L.lizec_chunk_write_degraded_host.restype = ctypes.c_int
     L.lizec_chunk_write_degraded_host.argtypes = degraded_args
+    repl_src = [ctypes.c_int, ctypes.c_int, u8p, ctypes.c_int, u32p, u64p,
+                u32p, u64p]
+    repl_dst = [u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u64p,
+                u32p, ctypes.c_int]
+    L.lizec_replicate_run_ragged.restype = ctypes.c_int
+    L.lizec_replicate_run_ragged.argtypes = [ctypes.c_void_p] + repl_src + \
+        repl_dst + [ctypes.c_uint64, ctypes.c_uint32, u32p]
+    L.lizec_replicate_ragged_host.restype = ctypes.c_int
+    L.lizec_replicate_ragged_host.argtypes = repl_src + repl_dst + \
+        [ctypes.c_uint32, u32p]
+    L.lizec_impl_replicate_ragged_check.restype = ctypes.c_int
+    L.lizec_impl_replicate_ragged_check.argtypes = repl_src + repl_dst + \
+        [ctypes.c_uint64, ctypes.c_uint32, u32p]
+    L.lizec_replicate_ragged_stages.restype = ctypes.c_int64
+    L.lizec_replicate_ragged_stages.argtypes = [
+        ctypes.c_int, ctypes.c_int, u32p, u64p, u32p, ctypes.c_int,
+        ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, u32p,
+        ctypes.c_uint64]
     _lib = L
     return _lib
 

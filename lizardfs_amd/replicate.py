@@ -8,6 +8,7 @@ part file.  Networking/disk stay with the host; this module does the whole
 compute pipeline on the GPU: recover -> per-block CRC -> assembled part
 image (header + big-endian CRC array + blocks) ready to pwrite.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -17,7 +18,7 @@ from . import crc as lcrc
 from . import lib as L
 from . import scrub
 from . import slice_traits as st
-from .ec import ReedSolomon
+from .ec import ReedSolomon, _pattern_tables
 
 
 def _rebuild_interleaved(rs, slice_type, fragments, erased, want, device):
@@ -383,3 +384,230 @@ def replicate_stream(k, m, host_parts, erased, want, chunk_ids, version,
             ctypes.POINTER(ctypes.c_uint64)),
         S, sub_batch), "lizec_replicate_run")
     return out
+
+
+StreamRebuild = collections.namedtuple("StreamRebuild", "images corrupt")
+StreamRebuild.__doc__ = """Result of replicate_stream_ragged: `images` maps
+(chunk index, part) to the part's image, `corrupt` maps a chunk index to the
+set of source parts that failed their CRC check (such chunks have no entry in
+`images`)."""
+
+REPL_INTERLEAVED = 1        # LIZEC_REPL_INTERLEAVED
+
+
+def _stream_ragged_prepare(k, m, host_parts, chunk_blocks, erased, want,
+                           chunk_ids, version, crcs, out, fmt):
+    """Every argument check of replicate_stream_ragged and the host arrays of
+    the C call; touches neither an engine nor the GPU."""
+    slice_type = st.ec_slice_type(k, m)
+    doff, coff, bstride, cstride = scrub.image_layout(fmt, slice_type)
+    nparts = k + m
+    if len(host_parts) != nparts:
+        raise ValueError(f"need {nparts} part slots")
+    cb = np.asarray(chunk_blocks)
+    if cb.ndim != 1 or cb.size < 1 or cb.dtype.kind not in "iu":
+        raise ValueError("chunk_blocks must be a 1-D int sequence")
+    if cb.min() < 1 or cb.max() > st.BLOCKS_IN_CHUNK:
+        raise ValueError(f"chunk_blocks out of [1, {st.BLOCKS_IN_CHUNK}]")
+    S = cb.size
+    if fmt == "moosefs" and len(chunk_ids) != S:
+        raise ValueError("need one chunk id per chunk")
+    pb = np.array([[st.number_of_blocks(slice_type, i, int(n))
+                    for i in range(nparts)] for n in cb], np.int64)
+    erased = ReedSolomon._per_stripe_sets(None, erased, S, "erased")
+    if want is not None:
+        want = ReedSolomon._per_stripe_sets(None, want, S, "want")
+    tables, index, pslots, pemask = _pattern_tables(k, m, erased, want)
+    slots = pslots[index]                                      # [S, oc]
+    oc = slots.shape[1]
+    palive = np.array([[i for i in range(nparts) if not (int(e) >> i) & 1]
+                       for e in pemask], np.intp)
+    alive = palive[index]                                      # [S, k]
+    src_nb = np.ascontiguousarray(
+        np.take_along_axis(pb, alive, axis=1).astype(np.uint32))
+    # blocks that are read of part i: the longest count among the chunks in
+    # which it survives
+    top = np.zeros(nparts, np.int64)
+    np.maximum.at(top, alive.ravel(), src_nb.ravel().astype(np.int64))
+    survives = np.zeros(nparts, bool)
+    survives[np.unique(alive)] = True
+    if crcs is not None and len(crcs) != nparts:
+        raise ValueError(f"crcs needs {nparts} part slots")
+    bases = np.zeros(nparts, np.uint64)
+    strides = np.zeros(nparts, np.uint64)
+    cbases = np.zeros(nparts, np.uint64)
+    cstrides = np.zeros(nparts, np.uint64)
+    for i in range(nparts):
+        if not survives[i]:
+            continue
+        a = host_parts[i]
+        if a is None:
+            raise ValueError(f"part {i} is None but survives in some chunk")
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or \
+                a.ndim != 2:
+            raise ValueError(f"part {i} must be a numpy uint8 [S, Lmax] array")
+        if a.shape[0] != S:
+            raise ValueError(f"part {i} has {a.shape[0]} rows, expected {S}")
+        _check_rows(a, f"part {i}")
+        if a.shape[1] < top[i] * st.BLOCK_SIZE:
+            raise ValueError(f"part {i}: rows of {a.shape[1]} bytes cannot "
+                             f"hold {int(top[i])} blocks")
+        bases[i] = a.ctypes.data
+        strides[i] = a.strides[0]
+        c = crcs[i] if crcs is not None else None
+        if c is None:
+            continue
+        if not isinstance(c, np.ndarray) or c.shape[0] != S or not (
+                (c.ndim == 2 and c.dtype == np.dtype(">u4")) or
+                (c.ndim == 3 and c.dtype == np.uint8 and c.shape[2] == 4)):
+            raise ValueError(f"crcs[{i}] must be [S, nmax] big-endian '>u4' "
+                             f"or [S, nmax, 4] uint8")
+        if c.shape[1] < top[i]:
+            raise ValueError(f"crcs[{i}]: rows of {c.shape[1]} CRCs cannot "
+                             f"cover {int(top[i])} blocks")
+        if c.strides[0] < 0 or (c.shape[1] > 1 and c.strides[1] != 4) or \
+                (c.ndim == 3 and c.strides[2] != 1):
+            raise ValueError(f"crcs[{i}]: a row's CRCs must be contiguous, "
+                             f"4 bytes apart, and the row stride not "
+                             f"negative")
+        cbases[i] = c.ctypes.data
+        cstrides[i] = c.strides[0]
+    rows = np.arange(S, dtype=np.uint64)[:, None]
+    src = np.where(src_nb > 0, bases[alive] + rows * strides[alive],
+                   np.uint64(0)).astype(np.uint64)
+    src_crc = None
+    if crcs is not None:
+        src_crc = np.where(cbases[alive] != 0,
+                           cbases[alive] + rows * cstrides[alive],
+                           np.uint64(0)).astype(np.uint64)
+    used = slots >= 0
+    dst_nb = np.take_along_axis(pb, np.maximum(slots, 0), axis=1)
+    dst_nb = np.ascontiguousarray(np.where(used, dst_nb, 0).astype(np.uint32))
+    head = doff if fmt == "moosefs" else 0
+    sizes = np.where(used, head + dst_nb.astype(np.int64) *
+                     (st.BLOCK_SIZE if fmt == "moosefs" else bstride), 0)
+    pairs = [(s, j) for s in range(S) for j in range(oc) if used[s, j]]
+    if out is not None:
+        for s, j in pairs:
+            key = (s, int(slots[s, j]))
+            if key not in out:
+                raise ValueError(f"out has no array for wanted image {key}")
+            a = out[key]
+            if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or \
+                    a.ndim != 1 or a.shape[0] != sizes[s, j]:
+                raise ValueError(f"out[{key}] must be a 1-D uint8 array of "
+                                 f"{int(sizes[s, j])} bytes")
+            if a.shape[0] > 1 and a.strides[0] != 1:
+                raise ValueError(f"out[{key}] must be contiguous")
+    sigs = np.zeros((S, oc, 22), np.uint8)
+    if fmt == "moosefs":
+        for s, j in pairs:
+            sig = scrub.build_signature(int(chunk_ids[s]), version,
+                                        slice_type, int(slots[s, j]))
+            sigs[s, j, :len(sig)] = np.frombuffer(sig, np.uint8)
+    return dict(S=S, oc=oc, tables=tables, index=index, slots=slots,
+                alive=alive, src=np.ascontiguousarray(src), src_nb=src_nb,
+                src_crc=src_crc, dst_nb=dst_nb, sizes=sizes, pairs=pairs,
+                sigs=sigs, head=head, coff=coff,
+                flags=REPL_INTERLEAVED if fmt == "interleaved" else 0)
+
+
+def _stream_ragged_run(k, p, out, alloc, call):
+    """Lay the images out (the caller's arrays, or one arena from `alloc`),
+    make the C call through `call` and sort its results."""
+    S, oc, slots, sizes = p["S"], p["oc"], p["slots"], p["sizes"]
+    dst = np.zeros((S, oc), np.uint64)
+    images = {}
+    if out is None:
+        # every image 16-aligned in one arena
+        offs = np.concatenate([[0], np.cumsum((sizes.ravel() + 15) & ~15)])
+        arena = alloc(max(int(offs[-1]), 1))
+        offs = offs[:-1].reshape(S, oc)
+        for s, j in p["pairs"]:
+            a = arena[int(offs[s, j]):int(offs[s, j] + sizes[s, j])]
+            images[(s, int(slots[s, j]))] = a
+            dst[s, j] = arena.ctypes.data + int(offs[s, j])
+    else:
+        for s, j in p["pairs"]:
+            a = out[(s, int(slots[s, j]))]
+            images[(s, int(slots[s, j]))] = a
+            # an empty INTERLEAVED image is nothing at all: not wanted
+            dst[s, j] = a.ctypes.data if a.shape[0] else 0
+    bad = np.zeros(S, np.uint32)
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    verify = p["src_crc"] is not None
+    src_crc = np.ascontiguousarray(p["src_crc"]) if verify else None
+    call(k, oc, p["tables"].ctypes.data_as(u8p), p["tables"].shape[0],
+         p["index"].ctypes.data_as(u32p), p["src"].ctypes.data_as(u64p),
+         p["src_nb"].ctypes.data_as(u32p),
+         src_crc.ctypes.data_as(u64p) if verify else None,
+         p["sigs"].ctypes.data_as(u8p), 22, p["head"], p["coff"],
+         dst.ctypes.data_as(u64p), p["dst_nb"].ctypes.data_as(u32p), S,
+         p["flags"], bad.ctypes.data_as(u32p) if verify else None)
+    corrupt = {}
+    for s in np.flatnonzero(bad):
+        s = int(s)
+        corrupt[s] = {int(p["alive"][s, j]) for j in range(k)
+                      if (int(bad[s]) >> j) & 1}
+        for j in range(oc):
+            images.pop((s, int(slots[s, j])), None)
+    return StreamRebuild(images, corrupt)
+
+
+def replicate_stream_ragged(k, m, host_parts, chunk_blocks, erased, want,
+                            chunk_ids, version, crcs=None, out=None, device=0,
+                            stage_bytes=0, fmt="moosefs"):
+    """replicate_stream for chunks of any length and erasure pattern, with
+    the sources verified on the way through (lizec_replicate_run_ragged):
+    surviving parts in HOST memory -> H2D -> CRC check -> recover -> per-block
+    CRC -> image assembly on-device -> D2H, double-buffered.
+
+    host_parts: k+m entries, numpy uint8 [S, Lmax] or None; row s of part i
+      is read only up to number_of_blocks(slice_type, i, chunk_blocks[s])
+      blocks.  Rows as for replicate_stream.  None only for a part that is
+      erased in every chunk.
+    chunk_blocks: S block counts in 1..1024.
+    erased / want: one index set for all chunks, or one per chunk (exactly m
+      erased each, want a subset), as for ReedSolomon.recover_batch_ragged.
+    crcs: optional list like host_parts of [S, nmax] big-endian '>u4' or
+      [S, nmax, 4] uint8 arrays: the CRC of every block of the part, as a
+      MooseFS part file holds them at offset 1024.  None = that part is not
+      verified.
+    out: optional dict (s, part) -> 1-D uint8 array of exactly the image's
+      size; otherwise the images are views into one pinned arena.
+    stage_bytes: device staging per pipeline slot (0 = 2 GiB).
+    fmt: "moosefs" or "interleaved"; chunk_ids and version are unused in the
+      latter.
+    Returns StreamRebuild(images, corrupt): images maps (s, part) to the
+    pwrite-ready image of that chunk's own size (header + nb*65536, or
+    nb*65540); corrupt maps s to the set of parts whose CRC check failed,
+    and those chunks are left out of images.
+    """
+    p = _stream_ragged_prepare(k, m, host_parts, chunk_blocks, erased, want,
+                               chunk_ids, version, crcs, out, fmt)
+    if not 0 <= stage_bytes <= 1 << 31:
+        raise ValueError("stage_bytes out of [0, 2^31]")
+    eng = L.engine(device)
+
+    def call(*a):
+        L.check(L.lib().lizec_replicate_run_ragged(
+            eng, *a[:-2], stage_bytes, *a[-2:]), "lizec_replicate_run_ragged")
+    return _stream_ragged_run(k, p, out, L.pinned_empty, call)
+
+
+def replicate_stream_ragged_host(k, m, host_parts, chunk_blocks, erased, want,
+                                 chunk_ids, version, crcs=None, out=None,
+                                 device=0, stage_bytes=0, fmt="moosefs"):
+    """replicate_stream_ragged on the CPU (lizec_replicate_ragged_host): same
+    arguments (device and stage_bytes are unused) and the same result byte
+    for byte; needs no GPU."""
+    p = _stream_ragged_prepare(k, m, host_parts, chunk_blocks, erased, want,
+                               chunk_ids, version, crcs, out, fmt)
+
+    def call(*a):
+        L.check(L.lib().lizec_replicate_ragged_host(*a),
+                "lizec_replicate_ragged_host")
+    return _stream_ragged_run(k, p, out, lambda n: np.empty(n, np.uint8),
+                              call)
